@@ -9,10 +9,14 @@ loss/compaction + forward/backward (1st + 2nd order) + RCCL gradient all-reduce 
 
 The timed state is config 2 as labelled: before the W warm-up steps the network is trained `--prepare` steps
 (default 800) so that every hash-grid level is active (the progressive schedule of grid.h:2427-2440 enables the
-last level at step 660). The fresh-network number (W warm-up + K timed steps from step 0, 4 active levels) is
-reported beside it as the `early_steps` leg.
+last level at step 660). With --full the fresh-network number (W warm-up + K timed steps from step 0, 4 active
+levels) is reported beside it as the `early_steps` leg.
 
-Usage: python bench.py --gpus N --steps K --warmup W
+Usage: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+  A plain run prepares, warms up, times the K steps and prints the result line (samples/s, ms_per_step and the timed
+  steps' own counters). --full adds every other measurement: the per-kernel replays and rooflines, the early-steps,
+  L=16, PSNR and marching-cubes legs and the CPU baseline. --dump-outputs DIR writes what the last timed step left
+  (parameters, EMA parameters, gradient, losses) as DIR/<name>.npy.
   N > 1: run under `torch.distributed.run` (one rank per GPU; WORLD_SIZE must equal N), or plainly, in which
   case this process starts `torch.distributed.run` itself as a child (before touching the GPU) and exits with
   its status.
@@ -74,6 +78,12 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=20)
+    # a plain run sets up, warms up, times the K steps and prints the headline line; --full adds every other measurement
+    # (the per-kernel replays and rooflines, the early / L=16 / PSNR / marching-cubes legs, the CPU baseline), each still
+    # switched by its own option below
+    p.add_argument("--full", action="store_true")
+    # what the last timed step left, as DIR/<name>.npy (dump_outputs)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None)
     # training steps before the warm-up: the all-levels state of config 2 (every level active from step 660)
     p.add_argument("--prepare", type=int, default=800)
     p.add_argument("--views", type=int, default=49)
@@ -406,23 +416,14 @@ def main():
     ms_step = elapsed / args.steps * 1e3
     lay = tb.layout()
     levels = min(st["valid_level"] + 1, lay["n_levels"])
-    # the dominant kernel as the training step runs it: after the timed region, INFER_STEPS more steps with hipEvents
-    # around each pre-compaction network launch (the progressive rounds' k_nerf_infer), the samples they evaluated
-    # from the device counter
-    it = tb.infer_timing(INFER_STEPS)
-    inf = step_inference(it, levels)
-    # per-kernel timing of the other kernels after that, on the final state (hipEvents on the testbed stream)
-    kern = kernel_rooflines(tb, levels)
-    per_step = {k: v["ms"] for k, v in kern.items() if k not in ("inference", "march_cut")}
-    per_step["inference_step"] = inf["ms_per_step"]
-    # the step's march: the cut march on the steps that cut it, the full march on the others (the replays time both)
-    fcut = d["mcut"] / max(1, args.steps)
-    per_step["march"] = round(fcut * kern["march_cut"]["ms"] + (1 - fcut) * kern["march"]["ms"], 4)
-    dom = max(per_step, key=per_step.get)
-    dk = inf if dom == "inference_step" else kern[dom]
-    mlp = ("mlp_train_rgb", "mlp_train_density")
-    mlp_ms = sum(kern[k]["ms"] for k in mlp)
-    tr = traffic_table()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tb, st, args.dump_outputs)
+    if args.full:
+        full = full_main_leg(tb, d, levels, args)
+        adam_b = full["kernels"]["adam_ema"]["bytes"]
+    else:
+        full = {}
+        adam_b = adam_bytes(tb)[0]
     out = {
         "metric": "training samples/sec (compacted NeuS2 training samples, DTU-scan24-shaped synthetic, base.json)",
         "value": value,
@@ -442,21 +443,10 @@ def main():
                    "dp_backend": args.dp_backend if world > 1 else None,
                    **({"same_device": True} if args.same_device and world > 1 else {}),
                    "prepare_steps": args.prepare, "levels_active": levels},
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": dk["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": dk["frac"], "traffic": measured_traffic(dom, levels), "bytes_per_launch": dk["bytes"],
-                     "units_per_launch": dk["units"], "launch_ms": dk["ms"], "levels_active": levels,
-                     "traffic_source": traffic_source(tr, dom, levels),
-                     **({k: inf[k] for k in ("launches_per_step", "evaluated_per_step", "ms_per_step", "steps", "note")}
-                        if dom == "inference_step" else {})},
+        **{k: full[k] for k in ("roofline",) if k in full},
         # the whole step against the HBM roofline and its MFMA rate
-        "roofline_step": step_roofline(d, levels, lay["n_params"], ms_step, args.steps, kern["adam_ema"]["bytes"]),
-        # the training MLP kernels (fwd recompute + 1st / 2nd-order backward + weight gradients) against the MFMA peak
-        "mfma_mlp_train": {"flops_per_sample": 43008 + 10240 + 28672, "ms": round(mlp_ms, 4),
-                           "tflops": round((43008 + 10240 + 28672) * batch / (mlp_ms * 1e-3) / 1e12, 1),
-                           "frac": round((43008 + 10240 + 28672) * batch / (mlp_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4)},
-        # memory-side line traffic (PMC, profiles/traffic.json) over the same launch: the hashed levels' 4-B corner
-        # gathers each move a 128-B line from the Infinity Cache, so this, not the algorithmic rate, is what binds
-        "line_traffic": line_traffic(measured_traffic(dom, levels), dk["ms"], dk["bytes"]),
+        "roofline_step": step_roofline(d, levels, lay["n_params"], ms_step, args.steps, adam_b),
+        **{k: full[k] for k in ("mfma_mlp_train", "line_traffic") if k in full},
         "progressive_steps_timed": d["progressive"],
         # steps whose later progressive rounds skipped the rays past the compaction cut (their network outputs
         # feed no training sample; the trained parameters are bitwise those without the cut, NEUS_PROG_CUT=0)
@@ -467,25 +457,87 @@ def main():
         "progressive_chunk_end": st["progressive_chunk_end"],
         "non_rollover_fraction": round(d["trained_real"] / max(1, batch * args.steps), 4),
         **({"exchange": {**d["exchange"], **rccl_info(args, rank)}} if "exchange" in d else {}),
-        "kernels": kern,
+        **{k: full[k] for k in ("kernels",) if k in full},
         "loss": st["ray_loss"],
         "prepare_s": round(prepare_s, 3),
     }
     del tb
-    if args.early:
+    if args.full and args.early:
         out["early_steps"] = early_leg(sc, grp, local, args)
-    if world == 1 and args.l16:
+    if args.full and world == 1 and args.l16:
         out["levels16"] = l16_leg(sc, grp, local, args)
-    if args.psnr_steps > 0:
+    if args.full and args.psnr_steps > 0:
         out["psnr"], tb2 = psnr_leg(sc, grp, local, args)
         if world == 1 and args.mc_res > 0:
             out["marching_cubes"] = marching_cubes_leg(tb2, args.mc_res)
         del tb2
-    if rank == 0 and args.cpu_baseline and world == 1:
+    if args.full and rank == 0 and args.cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(sc, args)
     if rank == 0:
         print(json.dumps(out), flush=True)
     grp.close()
+
+
+DUMP_GRID_SAMPLE = 1 << 21
+
+
+def dump_outputs(tb, st, path):
+    """--dump-outputs: what a caller of the timed path (Testbed.train_steps) holds after its last step, as float32
+    <name>.npy files under `path`: the fp32 master parameters, the EMA parameters and the last step's gradient - every
+    MLP weight and the variance, and of the hash grid the same DUMP_GRID_SAMPLE entries each (indices drawn once from a
+    fixed seed and the grid's size; 3 x 8 MB) - and the step's losses. The scene, the initial weights and the training
+    RNG are seeded, so two builds run with the same arguments are comparable entry for entry."""
+    import numpy as np
+    lay = tb.layout()
+    g0, ng = int(lay["grid_offset"]), int(lay["n_grid_params"])
+    idx = np.arange(int(lay["n_params"]), dtype=np.int64)
+    if ng > DUMP_GRID_SAMPLE:
+        pick = np.sort(np.random.default_rng(20240229).choice(ng, DUMP_GRID_SAMPLE, replace=False)) + g0
+        idx = np.concatenate([idx[:g0], pick, idx[g0 + ng:]])
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("params", tb.get_params()), ("ema_params", tb.get_ema_params()), ("gradients", tb.get_gradients())):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a[idx], dtype=np.float32))
+    np.save(os.path.join(path, "losses.npy"),
+            np.array([st[k] for k in ("loss", "ray_loss", "ek_loss", "mask_loss")], dtype=np.float32))
+
+
+def full_main_leg(tb, d, levels, args):
+    """--full, on the state the timed steps left: the pre-compaction network pass timed inside INFER_STEPS more steps, the
+    per-kernel replays and the rooflines of the dominant kernel and of the training MLP kernels."""
+    batch = args.batch
+    # the dominant kernel as the training step runs it: after the timed region, INFER_STEPS more steps with hipEvents
+    # around each pre-compaction network launch (the progressive rounds' k_nerf_infer), the samples they evaluated
+    # from the device counter
+    it = tb.infer_timing(INFER_STEPS)
+    inf = step_inference(it, levels)
+    # per-kernel timing of the other kernels after that, on the final state (hipEvents on the testbed stream)
+    kern = kernel_rooflines(tb, levels)
+    per_step = {k: v["ms"] for k, v in kern.items() if k not in ("inference", "march_cut")}
+    per_step["inference_step"] = inf["ms_per_step"]
+    # the step's march: the cut march on the steps that cut it, the full march on the others (the replays time both)
+    fcut = d["mcut"] / max(1, args.steps)
+    per_step["march"] = round(fcut * kern["march_cut"]["ms"] + (1 - fcut) * kern["march"]["ms"], 4)
+    dom = max(per_step, key=per_step.get)
+    dk = inf if dom == "inference_step" else kern[dom]
+    mlp = ("mlp_train_rgb", "mlp_train_density")
+    mlp_ms = sum(kern[k]["ms"] for k in mlp)
+    tr = traffic_table()
+    return {
+        "roofline": {"bound": "hbm", "kernel": dom, "achieved": dk["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": dk["frac"], "traffic": measured_traffic(dom, levels), "bytes_per_launch": dk["bytes"],
+                     "units_per_launch": dk["units"], "launch_ms": dk["ms"], "levels_active": levels,
+                     "traffic_source": traffic_source(tr, dom, levels),
+                     **({k: inf[k] for k in ("launches_per_step", "evaluated_per_step", "ms_per_step", "steps", "note")}
+                        if dom == "inference_step" else {})},
+        # the training MLP kernels (fwd recompute + 1st / 2nd-order backward + weight gradients) against the MFMA peak
+        "mfma_mlp_train": {"flops_per_sample": 43008 + 10240 + 28672, "ms": round(mlp_ms, 4),
+                           "tflops": round((43008 + 10240 + 28672) * batch / (mlp_ms * 1e-3) / 1e12, 1),
+                           "frac": round((43008 + 10240 + 28672) * batch / (mlp_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4)},
+        # memory-side line traffic (PMC, profiles/traffic.json) over the same launch: the hashed levels' 4-B corner
+        # gathers each move a 128-B line from the Infinity Cache, so this, not the algorithmic rate, is what binds
+        "line_traffic": line_traffic(measured_traffic(dom, levels), dk["ms"], dk["bytes"]),
+        "kernels": kern,
+    }
 
 
 def early_leg(sc, grp, device, args):

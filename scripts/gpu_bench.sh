@@ -1,13 +1,15 @@
 #!/bin/bash
 # Bench + rocprofv3 kernel-trace summary on the GPU box (no tests). Usage: bash scripts/gpu_bench.sh [steps] [warmup] [tag]
 R=${GRAFT_REPO_ROOT:-$(pwd)}
-cd "$R" && mkdir -p gpurun_out
+# every output goes under $NEUS_OUT_DIR (an absolute path; default: bench_out/ in the repository)
+OUT=${NEUS_OUT_DIR:-$R/bench_out}
+cd "$R" && mkdir -p "$OUT"
 STEPS=${1:-50}; WARM=${2:-100}; TAG=${3:-run}
-timeout -k 10 600 python bench.py --steps $STEPS --warmup $WARM --cpu-steps 6 > gpurun_out/bench_$TAG.log 2>&1
-rc=$?; echo "bench rc=$rc"; tail -3 gpurun_out/bench_$TAG.log
+timeout -k 10 600 python bench.py --full --steps $STEPS --warmup $WARM --cpu-steps 6 > $OUT/bench_$TAG.log 2>&1
+rc=$?; echo "bench rc=$rc"; tail -3 $OUT/bench_$TAG.log
 if [ $rc -ne 0 ]; then exit $rc; fi
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$R/gpurun_out/prof_$TAG" -o run -- python3 "$R/bench.py" --steps 20 --warmup 800 --cpu-baseline 0 > "$R/gpurun_out/prof_$TAG.log" 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$TAG" -o run -- python3 "$R/bench.py" --full --steps 20 --warmup 800 --cpu-baseline 0 > "$OUT/prof_$TAG.log" 2>&1
 rc=$?; echo "rocprof rc=$rc"
-[ $rc -eq 0 ] && python3 "$R/scripts/prof_summary.py" "$R/gpurun_out/prof_$TAG" --last-steps 16 > "$R/gpurun_out/prof_${TAG}_summary.md" && rm -rf "$R/gpurun_out/prof_$TAG"
+[ $rc -eq 0 ] && python3 "$R/scripts/prof_summary.py" "$OUT/prof_$TAG" --last-steps 16 > "$OUT/prof_${TAG}_summary.md" && rm -rf "$OUT/prof_$TAG"
 exit $rc

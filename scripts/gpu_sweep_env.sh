@@ -2,12 +2,14 @@
 # Bench sweep over an environment variable (driver shape, main leg only): bash scripts/gpu_sweep_env.sh TAG VAR "v1" "v2" ...
 # prints one line per value: VAR=value ms_per_step value(samples/s)
 R=${GRAFT_REPO_ROOT:-$(pwd)}
-cd "$R" && mkdir -p gpurun_out
+# every output goes under $NEUS_OUT_DIR (an absolute path; default: bench_out/ in the repository)
+OUT=${NEUS_OUT_DIR:-$R/bench_out}
+cd "$R" && mkdir -p "$OUT"
 TAG=$1; VAR=$2; shift 2
 for V in "$@"; do
-  env "$VAR=$V" timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --psnr-steps 0 --cpu-baseline 0 --l16 0 --early 0 --mc-res 0 ${BENCH_ARGS:-} \
-    > "gpurun_out/sweep_${TAG}_$(echo "$V" | tr ',/' '__').log" 2>&1 || { echo "bench failed for $VAR=$V"; exit 1; }
-  python3 - "$VAR" "$V" "gpurun_out/sweep_${TAG}_$(echo "$V" | tr ',/' '__').log" <<'PY'
+  env "$VAR=$V" timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 --psnr-steps 0 --cpu-baseline 0 --l16 0 --early 0 --mc-res 0 ${BENCH_ARGS:-} \
+    > "$OUT/sweep_${TAG}_$(echo "$V" | tr ',/' '__').log" 2>&1 || { echo "bench failed for $VAR=$V"; exit 1; }
+  python3 - "$VAR" "$V" "$OUT/sweep_${TAG}_$(echo "$V" | tr ',/' '__').log" <<'PY'
 import json, sys
 line = [l for l in open(sys.argv[3]) if l.startswith('{"metric"')][-1]
 d = json.loads(line)
