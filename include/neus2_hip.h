@@ -338,6 +338,17 @@ int neus_debug_scatter_stats(NeusTestbed* tb, uint64_t* records_per_level, uint3
 /* The region scatter's job plan: per level, the workgroups one level-local bucket is split over (1: not split; the heavy
  * buckets of the small dense levels meet through 64-bit integer atomics). */
 int neus_debug_scatter_parts(NeusTestbed* tb, uint32_t* parts_per_level /* n_levels */);
+/* Test hook: the grid-gradient scatter alone (launch_grid_scatter in the testbed's scatter mode, with its workspace) on
+ * caller-given device buffers; synchronous. n_cap (<= batch_size, else an error) is the leading dimension of the operand
+ * arrays: coords n_cap x coord_stride f32 (position in the first 3), dLdenc / genc [n_levels][n_cap] half2 (features 2l,
+ * 2l + 1: the paired layout of the training buffers), v n_cap float4 (dL/d(dL/dx) in xyz). n_valid (host, nullable:
+ * n_cap) <= n_cap is uploaded to a device word and read by the kernels as the step's device-side sample count: the
+ * operands of the samples past it are not used. grid_grad_out: 2 x n_entries f32 on the device; the entries of the
+ * levels up to valid_level are overwritten, those above it left alone in the region mode and zeroed in the binned ones
+ * (none of the testbed's own zero-range bookkeeping applies to a caller's buffer). */
+int neus_debug_grid_scatter(NeusTestbed* tb, void* hip_stream, uint32_t n_cap, const uint32_t* n_valid, const float* coords,
+                            uint32_t coord_stride, uint32_t valid_level, const void* dLdenc, const void* genc, const float* v,
+                            float* grid_grad_out);
 /* Development check of the single-pass exclusive scan the step's compactions use (scan.hip): device buffers in / out
  * of n u32 on `hip_stream`, `reps` launches on one fresh state (the epoch re-arm), synchronous; failures = bounded-wait
  * give-ups (0 expected). */

@@ -2745,6 +2745,28 @@ int neus_debug_scatter_parts(NeusTestbed* tb, uint32_t* parts_per_level) {
 		for (size_t j = 0; j < jobs.size() / 4; ++j) parts_per_level[jobs[4 * j]] = std::max(parts_per_level[jobs[4 * j]], jobs[4 * j + 2] >> 16);
 	});
 }
+int neus_debug_grid_scatter(NeusTestbed* tb, void* stream, uint32_t n_cap, const uint32_t* n_valid, const float* coords,
+                            uint32_t coord_stride, uint32_t valid_level, const void* dLdenc, const void* genc, const float* v,
+                            float* grid_grad_out) {
+	return guard([&] {
+		if (!tb->have_net) throw std::runtime_error("no network");
+		if (n_cap == 0 || n_cap > tb->batch) throw std::runtime_error("neus_debug_grid_scatter: n_cap must be in [1, batch_size]");
+		if (n_valid && *n_valid > n_cap) throw std::runtime_error("neus_debug_grid_scatter: n_valid exceeds n_cap");
+		if (coord_stride < 3) throw std::runtime_error("neus_debug_grid_scatter: coord_stride must be at least 3");
+		if (!coords || !dLdenc || !genc || !v || !grid_grad_out) throw std::runtime_error("neus_debug_grid_scatter: null buffer");
+		hipStream_t s = as_stream(tb, stream);
+		Dev<uint32_t> n_dev;
+		if (n_valid) {
+			n_dev.alloc(1);
+			HIP_CHECK(hipMemcpyAsync(n_dev.p, n_valid, 4, hipMemcpyHostToDevice, s));
+		}
+		// the caller's buffer: the plain workspace, as the HashGrid module's backward (no scatter_work_for)
+		launch_grid_scatter(s, n_dev.p, n_cap, n_cap, coords, coord_stride, tb->gl, valid_level, (const half_t*)dLdenc, (const half_t*)genc,
+		                    (const float4*)v, grid_grad_out, tb->swork, tb->scan_tmp.p, tb->scan_tmp_bytes);
+		HIP_CHECK(hipGetLastError());
+		HIP_CHECK(hipStreamSynchronize(s));
+	});
+}
 int neus_debug_march_profile(NeusTestbed* tb, unsigned long long* out, uint32_t max_waves, uint32_t* n_waves) {
 	return guard([&] {
 		if (!tb->have_net) throw std::runtime_error("no network");

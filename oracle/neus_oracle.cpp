@@ -26,6 +26,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <random>
@@ -386,8 +387,13 @@ static inline void half_atomic_add(uint16_t* p, uint16_t op) {
 		if (__atomic_compare_exchange_n(p, &old, nv, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) return;
 	}
 }
+// or_grid_scatter's side sums (null everywhere else; that function is serial): per grid parameter the sum of the
+// absolute values of the elementary adds, per grid entry the (sample, corner) hits
+static double* g_scatter_sabs = nullptr;
+static uint32_t* g_scatter_hits = nullptr;
 // one contribution `op32` (the reference's float product) to entry i of the level at parameter offset `off`
 static inline void grid_add(double* gg, size_t off, uint32_t i, double exact, float op32) {
+	if (g_scatter_sabs) g_scatter_sabs[off + i] += std::fabs(exact);
 	if (g_grid_grad_mode == 0) atomic_add_d(&gg[i], exact);
 	else if (g_grid_grad_mode == 1) atomic_add_d(&gg[i], (double)rh(op32));
 	else half_atomic_add(g_grid_half + off + i, f2h(op32));
@@ -408,6 +414,7 @@ static void grid_scatter_one(const Net& n, const float x[3], uint32_t valid_leve
 					else { w *= lp.pos[d]; pl[d] = lp.grid[d] + 1; }
 				}
 				uint32_t i = grid_index(lp.hsize, lp.res, pl);
+				if (g_scatter_hits) ++g_scatter_hits[(go + i) / 2];
 				grid_add(gg, go, i, (double)dL_denc[2 * l] * w, dL_denc[2 * l] * w);
 				grid_add(gg, go, i + 1, (double)dL_denc[2 * l + 1] * w, dL_denc[2 * l + 1] * w);
 			}
@@ -883,6 +890,83 @@ void or_network_backward(const OrNetCfg* c, const float* params, uint32_t n_el, 
 void or_network_backward_pos(const OrNetCfg* c, const float* params, uint32_t n_el, const float* coords, uint32_t valid_level,
                              const uint16_t* dL_dout, uint32_t indeed_batch_size, float* grads, float* dpos) {
 	network_backward_impl(c, params, n_el, coords, valid_level, dL_dout, indeed_batch_size, grads, dpos);
+}
+
+// -------------------------------------------------------------------------------------------
+// The grid-gradient scatter alone, on caller-given per-sample operands: x [n][3], dL_denc and g [n][2L] (fp16 values
+// passed as floats), v [n][3]. Two results over the grid's parameter index space (2 x entries, caller-zeroed):
+//  * the exact sum: grid_scatter_one in exact mode, every elementary add (8 first-order and 24 second-order per
+//    sample and level) unrounded in double; with it sabs, the sum of the absolute values of those adds (per add, not
+//    per corner after the corner's terms have cancelled), and hits [entries], the (sample, corner) pairs per entry;
+//  * emu (nullable): the rounding model of the device's scaled fp16 records written out on the CPU -
+//    each corner's contribution in fp32 with the device's operation order, runs of consecutive samples of one
+//    64-aligned group that hit the same entry with the same corner summed in fp32 (pairwise), the pair scaled
+//    by 2^k, k = clamp(14 - floor(log2 max(|a0|, |a1|)), 0, 31), rounded to fp16, added as round(v * 2^(38 - k)) to an
+//    int64, and the final sum converted to fp32. It is the format's arithmetic, not the kernels' binning. max_rec
+//    (nullable): the largest |record| before scaling (the format's domain is |a| < 2^15).
+// Serial: the sums are reproducible.
+// -------------------------------------------------------------------------------------------
+static inline void emu_record(const float* r0, const float* r1, uint32_t len, int64_t* acc, float* max_rec) {
+	const float a[2] = {sum_pairwise(r0, len), sum_pairwise(r1, len)};  // depth <= 6, as the device's segmented scan
+	const float m = std::max(std::fabs(a[0]), std::fabs(a[1]));
+	if (max_rec) *max_rec = std::max(*max_rec, m);
+	const int ex = m < std::numeric_limits<float>::min() ? -127 : std::ilogb(m);  // the biased exponent field - 127
+	const int k = std::min(std::max(14 - ex, 0), 31);
+	for (int f = 0; f < 2; ++f) {
+		const float r = std::min(std::max(rh(std::ldexp(a[f], k)), -65504.0f), 65504.0f);
+		acc[f] += (int64_t)std::llrint(std::ldexp((double)r, 38 - k));
+	}
+}
+void or_grid_scatter(const OrNetCfg* c, uint32_t n, const float* x, uint32_t valid_level, const float* dL_denc, const float* g,
+                     const float* v, double* sum, double* sabs, uint32_t* hits, float* emu, float* max_rec) {
+	Net net(*c);
+	const uint32_t L = net.c.n_levels;
+	const int saved_mode = g_grid_grad_mode;
+	g_grid_grad_mode = 0;
+	g_scatter_sabs = sabs; g_scatter_hits = hits;
+	for (uint32_t i = 0; i < n; ++i)
+		grid_scatter_one(net, x + 3 * (size_t)i, valid_level, dL_denc + 2 * (size_t)L * i, g + 2 * (size_t)L * i, v + 3 * (size_t)i, sum);
+	g_scatter_sabs = nullptr; g_scatter_hits = nullptr;
+	g_grid_grad_mode = saved_mode;
+	if (max_rec) *max_rec = 0.f;
+	if (!emu) return;
+	int64_t* acc = (int64_t*)std::calloc(net.n_grid_params, sizeof(int64_t));
+	for (uint32_t l = 0; l < L && l <= valid_level; ++l) {
+		int64_t* lacc = acc + (size_t)net.off[l] * 2;
+		for (uint32_t i0 = 0; i0 < n; i0 += 64) {
+			const uint32_t m = std::min(64u, n - i0);
+			LevelPos lp[64];
+			for (uint32_t j = 0; j < m; ++j) lp[j] = level_pos(net, l, x + 3 * (size_t)(i0 + j));
+			for (uint32_t idx = 0; idx < 8; ++idx) {
+				uint32_t run_e = 0, len = 0; float r0[64], r1[64];
+				for (uint32_t j = 0; j < m; ++j) {
+					const size_t i = i0 + j;
+					const LevelPos& p = lp[j];
+					float wc = 1.f; uint32_t pl[3];
+					for (int d = 0; d < 3; ++d) {
+						wc *= (idx & (1u << d)) ? p.pos[d] : 1.f - p.pos[d];
+						pl[d] = p.grid[d] + ((idx >> d) & 1u);
+					}
+					float w2 = 0.f;
+					for (int gd = 0; gd < 3; ++gd) {
+						float t = p.scale * v[3 * i + gd];
+						for (int d = 0; d < 3; ++d) if (d != gd) t *= (idx & (1u << d)) ? p.pos[d] : 1.f - p.pos[d];
+						w2 += (idx & (1u << gd)) ? t : -t;
+					}
+					const float* dl = dL_denc + 2 * (size_t)L * i + 2 * l;
+					const float* gg = g + 2 * (size_t)L * i + 2 * l;
+					const uint32_t e = grid_index(p.hsize, p.res, pl);  // 2 x the level-local entry
+					if (len && e != run_e) { emu_record(r0, r1, len, lacc + run_e, max_rec); len = 0; }
+					run_e = e;
+					r0[len] = dl[0] * wc + gg[0] * w2; r1[len] = dl[1] * wc + gg[1] * w2;
+					++len;
+				}
+				if (len) emu_record(r0, r1, len, lacc + run_e, max_rec);
+			}
+		}
+		for (size_t k = (size_t)net.off[l] * 2; k < (size_t)net.off[l + 1] * 2; ++k) emu[k] = (float)((double)acc[k] * (1.0 / 274877906944.0));
+	}
+	std::free(acc);
 }
 
 // -------------------------------------------------------------------------------------------

@@ -161,6 +161,25 @@ def network_backward_pos(cfg, params, coords, valid_level, dL_dout_u16, indeed_b
     return grads, dpos
 
 
+def grid_scatter(cfg, x, valid_level, dL_denc, g, v, emulate=True):
+    """or_grid_scatter: the grid-gradient scatter alone on per-sample operands x [n, 3], dL_denc / g [n, 2L] (fp16 values
+    as floats), v [n, 3]. Returns exact (float64 [2 E]: every elementary add unrounded), sabs (float64 [2 E]: the sum of
+    the absolute values of those adds), hits (uint32 [E]: (sample, corner) pairs per entry) and, with emulate, emu
+    (float32 [2 E]: the device's scaled-fp16-record / int64 rounding model on the same operands) with max_record, the
+    largest |record| before scaling."""
+    x, dL_denc, g, v = f32(x), f32(dL_denc), f32(g), f32(v)
+    n, L = x.shape[0], cfg.n_levels
+    assert x.shape == (n, 3) and dL_denc.shape == (n, 2 * L) and g.shape == (n, 2 * L) and v.shape == (n, 3)
+    n_grid = layout(cfg)["n_grid_params"]
+    exact, sabs = np.zeros(n_grid, np.float64), np.zeros(n_grid, np.float64)
+    hits = np.zeros(n_grid // 2, np.uint32)
+    emu = np.zeros(n_grid, np.float32) if emulate else None
+    max_rec = np.zeros(1, np.float32)
+    lib().or_grid_scatter(C.byref(cfg), C.c_uint32(n), P(x), C.c_uint32(valid_level), P(dL_denc), P(g), P(v), P(exact), P(sabs),
+                          P(hits), P(emu), P(max_rec))
+    return dict(exact=exact, sabs=sabs, hits=hits, emu=emu, max_record=float(max_rec[0]))
+
+
 class Dataset:
     """Host-side dataset view shared by oracle calls (RGBA8 images + ngp cameras)."""
 

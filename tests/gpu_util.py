@@ -1,7 +1,10 @@
 """Device-buffer plumbing for the GPU parity tests (torch only allocates and copies)."""
 import ctypes as C
+import os
 
 import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 _KEEP = []
@@ -39,3 +42,29 @@ def host(x, dtype):
 
 def ptr(x):
     return C.c_void_p(x.data_ptr() if x is not None else 0)
+
+
+def scatter_testbed(sc, mode, batch):
+    """A base.json testbed on scene sc in one of the grid-gradient scatter modes: "regions" (per-block record regions,
+    512-sample workgroups: the default), "regions1024" (1024-sample ones), "seg" (wide-block binning, 512), "seg1024" or
+    "binned" (the 256-sample histogram / scan / bin path)."""
+    from neus2_amd import pyngp
+    env = {"NEUS_SCATTER": {"binned": "binned", "seg": "wide", "seg1024": "wide"}.get(mode),
+           "NEUS_SCATTER_CHUNK": "1024" if mode.endswith("1024") else None}
+    old = {k: os.environ.get(k) for k in env}
+    for k, v in env.items():
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = v
+    try:
+        tb = pyngp.Testbed(pyngp.TestbedMode.Nerf)
+        tb.set_dataset(sc["images"], sc["focal"], sc["principal"], sc["xforms"], 1)
+        tb.reload_network_from_file(os.path.join(ROOT, "configs", "nerf", "base.json"), batch_size=batch)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    return tb

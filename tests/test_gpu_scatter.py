@@ -10,36 +10,11 @@ import os
 import numpy as np
 import pytest
 
-from gpu_util import dev, ptr
+from gpu_util import dev, ptr, scatter_testbed as _testbed
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _testbed(sc, mode, batch):
-    """mode: "regions" (per-block record regions, 512-sample workgroups: the default), "regions1024" (1024-sample
-    ones), "seg" (wide-block binning, 512), "seg1024" or "binned" (the 256-sample histogram / scan / bin path)."""
-    from neus2_amd import pyngp
-    env = {"NEUS_SCATTER": {"binned": "binned", "seg": "wide", "seg1024": "wide"}.get(mode),
-           "NEUS_SCATTER_CHUNK": "1024" if mode.endswith("1024") else None}
-    old = {k: os.environ.get(k) for k in env}
-    for k, v in env.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = v
-    try:
-        tb = pyngp.Testbed(pyngp.TestbedMode.Nerf)
-        tb.set_dataset(sc["images"], sc["focal"], sc["principal"], sc["xforms"], 1)
-        tb.reload_network_from_file(os.path.join(ROOT, "configs", "nerf", "base.json"), batch_size=batch)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    return tb
 
 
 @pytest.fixture(scope="module")

@@ -323,6 +323,17 @@ def _progress(msg):
 FLOOR_ORDERS = ("reversed", "pairwise", "blocked")
 
 
+def _variance_sum_depth(batch):
+    """Longest chain of fp32 additions a term of the variance gradient's batch sum passes through (mlp.hip
+    k_mlp_train_rgb, k_mlp_grad_reduce): the lane's serial loop over its wave's 32-sample chunks - the grid is
+    min(batch / 128, resident workgroups) workgroups of 4 waves, and at least one workgroup is resident on each of the 256
+    CUs; the 6-step shuffle tree; (s0 + s1) + (s2 + s3) over the workgroup's waves; in the reduction thread t's strided
+    loop over the workgroup partials t, t + 256, ... (at most 2048 of them) and the 8-step tree over the 256 threads."""
+    blocks_min = min(-(-batch // 128), 256)
+    blocks_max = min(-(-batch // 128), 2048)
+    return -(-batch // (128 * blocks_min)) + 6 + 2 + -(-blocks_max // 256) + 8
+
+
 def _teacher_forced_all_levels(sc, tag, progressive, n_steps=14, prepare=700, short_step=5, fixed_rays=False, prepare_batch=None,
                                batch=BATCH, floor_factor=1.5, level_bar=True):
     """Teacher-forced training at the all-levels state: the device trains `prepare` free-running steps
@@ -379,6 +390,8 @@ def _teacher_forced_all_levels(sc, tag, progressive, n_steps=14, prepare=700, sh
     floor_by_order = {o: {k: 0.0 for k in blocks} for o in FLOOR_ORDERS}
     lev_rel, lev_floor, lev_refop = np.zeros(cfg.n_levels), np.zeros(cfg.n_levels), np.zeros(cfg.n_levels)
     var_cond = 0.0  # the variance gradient's conditioning bar (below)
+    var_exact_ratio = 0.0  # the variance gradient against the device's own column sum: worst error / absolute bar
+    var_terms_min = batch  # ... and the fewest nonzero terms of that column over the steps (the check is not vacuous)
     prog0 = tb.stats()["progressive_steps"]
     short_seen, n_comp_equal, later_rounds, evaluated, kept = False, 0, 0, 0, 0
     records = []
@@ -407,6 +420,20 @@ def _teacher_forced_all_levels(sc, tag, progressive, n_steps=14, prepare=700, sh
         grid, bf = tb.get_density_grid()
         st1 = tb.stats()
         nreq_d, cc, ns_d = tb.ray_counts(tr.R)
+        # the variance gradient against the device's own batch, exactly: it is the fp32 sum, in a fixed tree, of column 7
+        # of the step's compacted fp16 dL/doutput (after the rollover's copies, which the step's encode writes into the same
+        # buffer), so it sits within depth x 2^-24 x sum |x| of that column's float64 sum - an absolute bar that does not
+        # widen when the terms cancel, unlike the conditioning bar against the oracle's batch below. The buffer holds the
+        # step's batch under every option this function runs with: the lookahead of the next step samples rays into
+        # buffers of its own and the next loss, which rewrites dL/doutput, runs inside the next step.
+        dl_dev = np.zeros((batch, 16), np.uint16)
+        check(lib().neus_debug_get_batch(tb.handle, None, C.c_void_p(dl_dev.ctypes.data), None))
+        col7 = dl_dev.view(np.float16)[:, 7].astype(np.float64)
+        var_err = abs(g[lay["variance_offset"]] - col7.sum())
+        var_bar = _variance_sum_depth(batch) * 2.0 ** -24 * np.abs(col7).sum()
+        var_exact_ratio = max(var_exact_ratio, var_err / max(var_bar, 1e-300))
+        var_terms_min = min(var_terms_min, int(np.count_nonzero(col7)))
+        assert np.all(np.isfinite(col7)) and np.count_nonzero(col7) > 0 and var_err <= var_bar, (k, float(g[lay["variance_offset"]]), col7.sum(), var_err, var_bar)
         step_prog = st1["progressive_steps"] > prog_before
         step_later = int((cc > chunk_end).sum()) if step_prog else 0
         later_rounds += step_later
@@ -474,7 +501,8 @@ def _teacher_forced_all_levels(sc, tag, progressive, n_steps=14, prepare=700, sh
             **{f"floor_rel_{k}": v for k, v in floor.items()},
             **{f"floor_{o}_{k}": v for o, d in floor_by_order.items() for k, v in d.items()},
             **{f"floor_rel_grid_L{l}": lev_floor[l] for l in range(cfg.n_levels)},
-            **{f"ref_operand_rel_grid_L{l}": lev_refop[l] for l in range(cfg.n_levels)}, variance_conditioning_bar=var_cond)
+            **{f"ref_operand_rel_grid_L{l}": lev_refop[l] for l in range(cfg.n_levels)}, variance_conditioning_bar=var_cond,
+            variance_exact_err_over_bar=var_exact_ratio, variance_exact_nonzero_terms_min=var_terms_min)
     st = tb.stats()
     assert prog >= n_steps - 1, (f"progressive inference ran on {prog} of {n_steps} steps (last step: {st['measured_batch_size']} "
                                  f"compacted of {st['measured_batch_size_before_compaction']} requested)")

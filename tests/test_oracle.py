@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+import scatter_cases as SC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -475,3 +476,131 @@ def test_oracle_grid_grad_modes():
         assert r_hf.max() >= r_op.max() * 0.5, (scale, r_hf, r_op)
         rng_d = np.random.default_rng(7)
         np.testing.assert_array_equal(grads(scale, "exact"), ex)
+
+
+# ---------------------------------------------------------------- the grid-gradient scatter's exact references
+def _np_scatter_terms(cfg, x, dl, g, v, valid_level):
+    """Plain numpy restatement of the hash-grid gradient (first order dL/denc * w_corner, second order
+    g * (+/-) scale v_d prod w_other; weights in fp32 as the kernels compute them): yields per level and corner
+    (param index of feature 0 [n], first-order terms [n, 2] and the three second-order terms [n, 3, 2], float64)."""
+    off, res, scale, _ = O.grid_tables(cfg)
+    x = np.asarray(x, np.float32)
+    for l in range(min(cfg.n_levels, valid_level + 1)):
+        hs = np.uint32(int(off[l + 1]) - int(off[l]))
+        # pos_fract: fmaf(x, scale, 0.5) - evaluated exactly in float64, then rounded once (x, scale are fp32: the
+        # product is exact in float64, the sum with 0.5 correctly rounded unless a double rounding tie: not at these inputs)
+        p = (x.astype(np.float64) * np.float64(scale[l]) + 0.5).astype(np.float32)
+        fl = np.floor(p)
+        pos = (p - fl).astype(np.float32)
+        cell = fl.astype(np.int64)
+        for idx in range(8):
+            bit = [(idx >> d) & 1 for d in range(3)]
+            f = [pos[:, d] if bit[d] else np.float32(1) - pos[:, d] for d in range(3)]
+            w = (np.float32(1) * f[0]) * f[1] * f[2]
+            c = [((cell[:, d] + bit[d]) & 0xFFFFFFFF).astype(np.uint32) for d in range(3)]
+            r = np.uint32(res[l])
+            stride, index, dims = 1, np.zeros(len(x), np.uint32), 0
+            while dims < 3 and stride <= int(hs):
+                index = index + c[dims] * np.uint32(stride & 0xFFFFFFFF)
+                stride *= int(r)
+                dims += 1
+            if int(hs) < stride:
+                index = c[0] ^ (c[1] * np.uint32(2654435761)) ^ (c[2] * np.uint32(805459861))
+            e = 2 * (int(off[l]) + (index % hs).astype(np.int64))
+            first = dl[:, 2 * l:2 * l + 2].astype(np.float64) * w.astype(np.float64)[:, None]
+            second = np.zeros((len(x), 3, 2))
+            for gd in range(3):
+                t = np.float32(scale[l]) * v[:, gd].astype(np.float32)
+                for d in range(3):
+                    if d != gd:
+                        t = t * f[d]
+                sgn = 1.0 if bit[gd] else -1.0
+                second[:, gd, :] = g[:, 2 * l:2 * l + 2].astype(np.float64) * (sgn * t.astype(np.float64))[:, None]
+            yield l, idx, e, first, second
+
+
+def test_grid_scatter_exact_matches_numpy():
+    """or_grid_scatter's exact sum, S (absolute values per elementary add, before any cancellation inside a corner) and
+    hit counts against a plain float64 numpy restatement: in-cube and outside-cube positions (negative cells, wrap on the
+    dense and the hashed levels), repeated positions, valid level 13 and 2."""
+    cfg = O.make_cfg(n_levels=14)
+    rng = np.random.default_rng(5)
+    n = 192
+    x = rng.uniform(-0.4, 1.4, (n, 3)).astype(np.float32)
+    x[:64] = rng.uniform(0.02, 0.98, (64, 3))
+    x[64:72] = np.float32([[-1e-3, 0.5, 0.5], [1.0, 1.0, 1.0], [-2.5, 3.0, 0.2], [0.5, -0.75, 1.9],
+                           [1.0 - 1e-7, 0.0, 0.0], [0.0, 0.0, 0.0], [7.0, -7.0, 0.5], [0.25, 0.5, -1e-6]])
+    x[100:120] = x[100]
+    dl = rng.normal(0, 1e-2, (n, 28)).astype(np.float16).astype(np.float32)
+    g = rng.normal(0, 1e-2, (n, 28)).astype(np.float16).astype(np.float32)
+    v = rng.normal(0, 1e-3, (n, 3)).astype(np.float32)
+    for valid in (13, 2):
+        r = O.grid_scatter(cfg, x, valid, dl, g, v, emulate=False)
+        ex, sa, hits = np.zeros_like(r["exact"]), np.zeros_like(r["sabs"]), np.zeros_like(r["hits"])
+        for l, idx, e, first, second in _np_scatter_terms(cfg, x, dl, g, v, valid):
+            for f in range(2):
+                np.add.at(ex, e + f, first[:, f] + second[:, :, f].sum(axis=1))
+                np.add.at(sa, e + f, np.abs(first[:, f]) + np.abs(second[:, :, f]).sum(axis=1))
+            np.add.at(hits, e // 2, 1)
+        np.testing.assert_array_equal(r["hits"], hits)
+        assert hits.sum() == n * 8 * (valid + 1)
+        # float64 sums in another order: a few ulps of the absolute sum
+        assert np.all(np.abs(r["exact"] - ex) <= 1e-13 * sa)
+        assert np.all(np.abs(r["sabs"] - sa) <= 1e-13 * sa)
+        assert np.any(sa > 4 * np.abs(ex))  # cancellation inside an entry: S is not |exact|
+
+
+def test_grid_scatter_record_emulation_known_answers():
+    """The emulation of the device's record format on records worked out by hand in numpy: consecutive samples in
+    far-apart cells (no run merges), so every (sample, corner) is one record fp16(a 2^k) with the pair's shared
+    k = clamp(14 - floor(log2 max|a|), 0, 31), added as round(. 2^(38 - k)) to an int64. Operand scales from 2^-22 to 2000
+    (k = 31 clamped with fp16-subnormal records up to k = 0: |a| ~ 30000), a pair 2^20 apart, a zero sample."""
+    cfg = O.make_cfg(n_levels=14)
+    rng = np.random.default_rng(6)
+    n = 48
+    x = rng.uniform(0.1, 0.4, (n, 3)).astype(np.float32)
+    x[1::2] += np.float32(0.5)
+    x[0] = np.float32(2.5 / 15)  # a vertex of level 0 (scale 15): one corner's weight is ~1, so |a| ~ 30000 there: k = 0
+    sig = np.exp2(rng.integers(-22, 5, n)).astype(np.float64)
+    sig[:6] = [12000.0, 1200.0, 2.0 ** -22, 2.0 ** -30, 0.0, 1.0]
+    dl = (rng.normal(0, 1, (n, 28)) * sig[:, None])
+    dl[5, 1::2] *= 2.0 ** -20
+    dl[0, :2] = [30000.0, -29000.0]
+    dl = dl.astype(np.float16).astype(np.float32)
+    zero = np.zeros((n, 28), np.float32)
+    r = O.grid_scatter(cfg, x, 13, dl, zero, np.zeros((n, 3), np.float32))
+    acc = np.zeros(r["exact"].size, np.int64)
+    ks = set()
+    for l, idx, e, first, second in _np_scatter_terms(cfg, x, dl, zero, np.zeros((n, 3), np.float32), 13):
+        a = first.astype(np.float32)  # dl * w: one fp32 rounding (the product is exact in float64)
+        m = np.abs(a).max(axis=1)
+        with np.errstate(divide="ignore"):
+            ex = np.where(m > 0, np.floor(np.log2(m, where=m > 0, out=np.full(n, -127.0))), -127.0)
+        k = np.clip(14 - ex, 0, 31).astype(np.int64)
+        ks.update(int(q) for q in k)
+        for f in range(2):
+            h = np.ldexp(a[:, f].astype(np.float64), k).astype(np.float16)  # a 2^k is exact; one rounding to fp16
+            np.add.at(acc, e + f, np.rint(np.ldexp(h.astype(np.float64), 38 - k)).astype(np.int64))
+    want = (acc.astype(np.float64) * 2.0 ** -38).astype(np.float32)
+    assert {0, 31} <= ks and len(ks) > 20
+    np.testing.assert_array_equal(r["emu"].view(np.uint32), want.view(np.uint32))
+    assert r["max_record"] < 2.0 ** 15
+
+
+@pytest.mark.parametrize("name", SC.NAMES)
+def test_grid_scatter_emulation_within_bound(name):
+    """The per-entry bound the device's scatter is held to (scatter_cases.bound, derived in DESIGN §6 from the record
+    format alone) is not too tight: the CPU emulation of that format stays inside it against the exact sum on every input
+    set of the device test. Domain of the bound, asserted here: every record |a| < 2^15 (the scale k >= 0 keeps
+    a 2^k below fp16's overflow) and every per-entry sum below the int64 accumulator's 2^25."""
+    c = SC.case(name)
+    assert c["max_record"] < 2.0 ** 15
+    assert np.abs(c["exact"]).max() < 2.0 ** 25 and c["sabs"].max() < 2.0 ** 25
+    assert int(c["hits"].sum()) == c["n_valid"] * 8 * (c["valid_level"] + 1)
+    end = 2 * c["offsets"][c["valid_level"] + 1]
+    assert not np.any(c["emu"][end:]) and not np.any(c["exact"][end:])
+    for l, ratio, n_past, rel in SC.level_metrics(c, c["emu"]):
+        assert n_past == 0 and ratio <= 1.0, (name, l, ratio, n_past)
+        assert (rel is None) == (name == "small_zero"), (name, l)
+    if name == "small_zero":
+        assert not np.any(c["emu"].view(np.uint32))
