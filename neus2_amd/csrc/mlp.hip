@@ -26,6 +26,7 @@
 #include "scan_lookback.h"
 #include "grid_common.h"
 #include "occ_common.h"
+#include "options.h"
 // the loss's alpha terms (fused inference epilogue) keep the march / loss files' arithmetic: no FMA contraction, so they
 // are bitwise k_loss_alpha's (march.hip) and the oracle's
 #pragma clang fp contract(off)
@@ -1696,13 +1697,12 @@ void launch_nerf_infer(hipStream_t s, uint32_t L, uint32_t W, const uint32_t* n_
                        uint32_t valid_level, const half_t* grid, const MlpPtrs& w, half_t* out, uint32_t blocks, const uint32_t* idx,
                        const InferAlpha* ia) {
 	InferAlpha a = ia ? *ia : InferAlpha{nullptr, nullptr, 0.f, 0u, nullptr};
-	static const bool xcd_parts = [] { const char* e = std::getenv("NEUS_INFER_XCD_PARTS"); return e && e[0] == '1'; }();
-	if (xcd_parts) a.xcd_parts = 8u;
+	const NeusProcessOptions& po = process_options();
+	if (po.infer_xcd_parts) a.xcd_parts = 8u;
 	// persistent grid: at most the resident capacity (weights are staged once per block; both variants run at the
 	// same 3 waves per SIMD, amdgpu_waves_per_eu)
-	static const bool pipe = [] { const char* e = std::getenv("NEUS_INFER_PIPE"); return !(e && e[0] == '0'); }();
-	const bool all = pipe && valid_level + 1 >= L;
-	static const uint32_t grid_cap = [] { const char* e = std::getenv("NEUS_INFER_GRID"); return e ? (uint32_t)std::atoi(e) : 0u; }();  // (development)
+	const bool all = po.infer_pipe && valid_level + 1 >= L;
+	const uint32_t grid_cap = po.infer_grid;  // (development)
 	auto xg = [&](uint32_t b) { if (grid_cap) b = std::min(b, grid_cap); return a.xcd_parts ? std::max(8u, b & ~7u) : b; };
 	dbg_lds_gate(s);
 	const hipEvent_t ev0 = g_infer_ev[0], ev1 = g_infer_ev[1];
@@ -1849,7 +1849,7 @@ uint32_t mlp_train_blocks(uint32_t L, uint32_t W, uint32_t n) {
 		cap = std::min(cap, c); }
 	NEUS_MLP_CONFIGS(X)
 #undef X
-	static const uint32_t pct = [] { const char* e = std::getenv("NEUS_MLP_BLOCKS_PCT"); return e ? (uint32_t)std::atoi(e) : 100u; }();
+	const uint32_t pct = process_options().mlp_blocks_pct;
 	if (pct > 0 && pct != 100) cap = std::max<uint32_t>(1, cap * pct / 100);  // development: a smaller (or over-decomposed) grid
 	return std::max<uint32_t>(1, std::min<uint32_t>((n + 127) / 128, cap));
 }

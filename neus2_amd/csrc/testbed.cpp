@@ -12,6 +12,7 @@
 #include "scan_lookback.h"
 #include "json_lite.h"
 #include "hostgroup.h"
+#include "options.h"
 #include "../../include/neus2_hip.h"
 
 #include <rccl/rccl.h>
@@ -49,19 +50,15 @@ thread_local std::string g_err;
 		if (r_ != ncclSuccess) throw std::runtime_error(std::string(#x) + " failed: " + ncclGetErrorString(r_)); \
 	} while (0)
 
-// Debug: NEUS_DBG_POISON="byte[:lo:hi]" fills the fresh device allocations number lo .. hi-1 (counted from the last
-// testbed creation) with `byte`; NEUS_DBG_ALLOC_LOG=1 lists them (number, bytes) on stderr. A result that changes with
-// the fill reads memory no kernel wrote (i.e. depends on what a recycled allocation held). Off: one getenv per alloc.
+// Debug (options.h NeusAllocDebug): the fill / the listing of the fresh device allocations, numbered from the last
+// neus_testbed_create, where the pair is latched for the process
 std::atomic<uint64_t> g_alloc_seq{0}, g_alloc_base{0};
+NeusAllocDebug g_alloc_dbg;
 void dbg_poison(void* p, size_t bytes) {
 	const uint64_t k = g_alloc_seq++ - g_alloc_base.load();
-	if (std::getenv("NEUS_DBG_ALLOC_LOG")) std::fprintf(stderr, "neus alloc %llu %zu\n", (unsigned long long)k, bytes);
-	const char* e = std::getenv("NEUS_DBG_POISON");
-	if (!e) return;
-	unsigned v = 0;
-	unsigned long long lo = 0, hi = ~0ull;
-	if (std::sscanf(e, "%u:%llu:%llu", &v, &lo, &hi) < 1) return;
-	if (k >= lo && k < hi) HIP_CHECK(hipMemset(p, (int)v, bytes));
+	const NeusAllocDebug& d = g_alloc_dbg;
+	if (d.log) std::fprintf(stderr, "neus alloc %llu %zu\n", (unsigned long long)k, bytes);
+	if (d.poison && k >= d.lo && k < d.hi) HIP_CHECK(hipMemset(p, (int)d.byte, bytes));
 }
 
 template <class T> struct Dev {
@@ -176,32 +173,28 @@ struct NeusLocalGroup {
 };
 
 struct NeusTestbed {
+	const NeusOptions opt = NeusOptions::from_env();  // the NEUS_* switches, read once: they hold for the testbed's life
 	int device = 0;
 	hipStream_t stream = nullptr;
 	// side stream of the backward: the weight-gradient GEMM runs there beside the grid scatter (disjoint inputs and
 	// outputs; both deterministic), forked from and joined back into the step's stream by events
 	hipStream_t aux_stream = nullptr;
 	hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-	// Lookahead (NEUS_LOOKAHEAD): the next step's ray sampling (ray generation, march, march write, ray sort) issued on
-	// la_stream right after this step's loss, beside its backward and optimizer, which read none of its outputs. Only
-	// between steps of one neus_testbed_train call (nothing pending between calls), at one rank, on static scenes, and
-	// not before a step that starts with an occupancy update or a loss readback (train_step: la_go).
-	bool la_on = [] { const char* e = std::getenv("NEUS_LOOKAHEAD"); return !(e && e[0] == '0'); }();
-	// adam_overlap: the step's Adam parameters; next: the first parameter not issued; on: the exchange stream the pieces
+	// Lookahead (opt.lookahead): the next step's ray sampling (ray generation, march, march write, ray sort) issued on
+	// la_stream behind this step's counters (their stream: the step's, or the exchange stream with a group), beside its
+	// backward and optimizer, which read none of its outputs. At any world size; only between steps of one
+	// neus_testbed_train call (nothing pending between calls), on static scenes, and not before a step that starts with an
+	// occupancy update or a loss readback (train_step: la_go).
+	// opt.adam_overlap: the step's Adam parameters; next: the first parameter not issued; on: the exchange stream the pieces
 	// follow their ranges' all-reduces on (data parallel), or null (one rank: ad_stream, behind the step's stream)
 	struct AdamSplit { AdamParams p; uint32_t next; hipStream_t on; };
 	bool la_pending = false, la_next_in_call = false;
 	uint64_t la_steps = 0, adam_split_steps = 0;  // (stats: lookahead_steps, adam_split_steps)
-	const bool la_stat = [] { const char* e = std::getenv("NEUS_LA_STAT"); return e && e[0] == '1'; }();
-	// Where in the backward the lookahead is issued (one rank; with a group it goes out with the counters' exchange):
-	// 0 right after the loss, 1 after the training encode, 2 after the training MLP kernels, 3 after the weight-gradient
-	// reduction, 4 after the scatter. A cut march's sampling is small and goes after the encode (it then no longer shares
-	// the gather-bound encode: 0.770 -> 0.759 ms/step at step 800, 0.876 -> 0.854 at step 1600,
-	// profiles/r06la_issue_point_ab.txt); a full march needs the whole backward to hide in and goes right after the loss
-	// (round 5: 1 as 0, 2 and 3 slower, r05la_issue_point_ab.txt). NEUS_LA_AT / NEUS_LA_AT_FULL override the two.
-	const int la_at_cut = [] { const char* e = std::getenv("NEUS_LA_AT"); return e ? std::atoi(e) : 1; }();
-	const int la_at_full = [] { const char* e = std::getenv("NEUS_LA_AT_FULL"); return e ? std::atoi(e) : 0; }();
-	int la_at = 0;  // the pending lookahead's issue point
+	// Where in the backward the pending lookahead is issued (one rank; with a group it goes out with the counters'
+	// exchange): 0 right after the loss, 1 after the training encode, 2 after the training MLP kernels, 3 after the
+	// weight-gradient reduction, 4 after the scatter. A cut march's sampling is small and goes after the encode, where it no
+	// longer shares the gather-bound encode (opt.la_at_cut); a full march goes right after the loss (opt.la_at_full).
+	int la_at = 0;
 	std::function<void()> la_deferred;
 	void la_fire(int at) {
 		if (la_deferred && at >= la_at) { auto f = std::move(la_deferred); la_deferred = nullptr; f(); }
@@ -306,7 +299,6 @@ struct NeusTestbed {
 	Dev<float> density_grid, density_tmp, grid_mean, grid_partial, occ_pos, occ_density;
 	Dev<uint32_t> occ_idx;
 	Dev<uint32_t> occ_ulist;  // the cell-ordered uniform samples, OccSampling::ulist
-	bool occ_sort = true;     // NEUS_OCC_SORT=0: uniform samples in index order (A/B reference)
 	Dev<uint8_t> bitfield;
 	Dev<uint32_t> bf_lin;   // mip-0 occupancy in (x, y, z/32) word order for the constant-step march
 	Dev<float> occ_bbox;    // world box of the occupied cells of every mip (+ stage-1 scratch): the ray generation's cull
@@ -314,14 +306,12 @@ struct NeusTestbed {
 	float bias_b1 = -1.f, bias_b2 = -1.f;
 	bool bias_conv = false;
 	Dev<uint32_t> dbg_enc;  // debug timing only (neus_debug_time_kernel 11): [L][16 Nc] encodings of the inference samples
-	bool ray_cull = true;   // NEUS_RAY_CULL=0: march every ray (A/B reference)
 	uint32_t dbg_lds_fill = 0;  // tests (neus_debug_set_lds_fill): garbage-fill every CU's LDS before the step's march write
-	bool dbg_loss_replay = [] { const char* e = std::getenv("NEUS_DBG_LOSS_REPLAY"); return e && e[0] == '1'; }();
 	Dev<float> dbg_co; Dev<half_t> dbg_dl;
 	static constexpr int DBG_SNAP_N = 15;
 	Dev<uint8_t> dbg_snap[DBG_SNAP_N];  // the loss-gradient inputs right after its launch (ids 0..14 of neus_debug_get_buffer)
-	uint32_t dbg_lds_fill_all = 0;
-	uint32_t dbg_xcd_shift = 0;  // tests (neus_debug_set_xcd_shift): workgroups of a no-op kernel before every kernel of the step  // tests (neus_debug_set_lds_fill_all): ... before every kernel of the step (g_dbg_lds_fill)
+	uint32_t dbg_lds_fill_all = 0;  // tests (neus_debug_set_lds_fill_all): ... before every kernel of the step (g_dbg_lds_fill)
+	uint32_t dbg_xcd_shift = 0;     // tests (neus_debug_set_xcd_shift): workgroups of a no-op kernel before every kernel of the step
 	Dev<PcgJump> pcg_tab;   // pcg32 jump-ahead table (common.h PcgJumpTable)
 	uint32_t density_grid_ema_step = 0;
 	uint64_t occ_samples = 0;  // occupancy-grid samples this rank evaluated since the network was loaded
@@ -350,7 +340,6 @@ struct NeusTestbed {
 	Dev<uint16_t> sc_rtab;
 	std::vector<uint32_t> sc_jobs2_before;  // [L + 1] region-scatter jobs of the levels below l
 	uint32_t sc_zero_from_e = 0;            // region scatter: grid entries from here on hold zero gradients
-	bool scatter_noskip = false;            // NEUS_SCATTER_NOSKIP=1: zero the grid gradient every step (A/B reference)
 	Dev<h2> sc_rec_g;
 	Dev<uint16_t> sc_rec_i;
 	// restructured loss scratch (kernels.h LossWork)
@@ -361,8 +350,8 @@ struct NeusTestbed {
 	// progressive (cut-off-aware) inference: 0 off, 1 auto (when under PROGRESSIVE_RATIO of the kept samples were
 	// composited at the last loss readback), 2 always; chunk ends of the rounds before the last (march.hip)
 	int progressive_mode = 1;
-	std::vector<uint32_t> chunk_ends{32, 64, 96};  // NEUS_CHUNK_ENDS="e0,e1,..." at creation overrides (A/B of schedules)
-	std::vector<uint32_t> chunk_ends_cut;          // the chunk ends of a cut step (chosen with chunk_ends; empty: chunk_ends)
+	std::vector<uint32_t> chunk_ends = opt.chunk_ends.empty() ? std::vector<uint32_t>{32, 64, 96} : opt.chunk_ends;
+	std::vector<uint32_t> chunk_ends_cut;  // the chunk ends of a cut step (chosen with chunk_ends; empty: chunk_ends)
 	const std::vector<uint32_t>& ends_for(bool cut) const { return cut && !chunk_ends_cut.empty() ? chunk_ends_cut : chunk_ends; }
 	// Chunk ends chosen from the training state (chunk_auto: no explicit ends given): at each loss readback the mean
 	// composited samples per ray with samples, mc (all-reduced counters: the same on every rank), sets three rounds
@@ -370,7 +359,7 @@ struct NeusTestbed {
 	// 2^18, profiles/r04fg_chunk_ends_sweep.txt, r04hi_*): step 800 (mc ~117) best at e = 64 (1.237 ms vs 1.283 for
 	// {32, 64, 96}), step 1600 (mc ~39) best at e = 32 (1.203 ms vs 1.308 for e = 64). The rounds only change which
 	// samples are evaluated, never a result (bit-identical to the one pass).
-	bool chunk_auto = true;
+	bool chunk_auto = opt.chunk_ends.empty();
 	void choose_chunk_ends(uint32_t composited, uint32_t rays_with_samples) {
 		if (!chunk_auto || rays_with_samples == 0) return;
 		const float mc = (float)composited / (float)rays_with_samples;
@@ -378,22 +367,18 @@ struct NeusTestbed {
 		chunk_ends.assign({e, 2 * e});
 		// With the compaction cut (and the march cut) the later rounds see only the rays before the cut (a few thousand at
 		// the bench's shape), so their fixed cost - launches, scans, the cut - outweighs the samples a third round saves:
-		// two rounds, the first twice as long (steps 800 / 1600: 0.815 / 0.895 -> 0.773 / 0.878 ms/step,
-		// profiles/r06y_chunk_ends_cut_sweep.txt). NEUS_CHUNK_SCALE / NEUS_CHUNK_ROUNDS (2 or 3) override, for sweeps.
-		static const float scale = [] { const char* v = std::getenv("NEUS_CHUNK_SCALE"); return v ? (float)std::atof(v) : 2.f; }();
-		static const int rounds = [] { const char* v = std::getenv("NEUS_CHUNK_ROUNDS"); return v ? std::atoi(v) : 2; }();
-		const uint32_t ec = std::min(256u, std::max(24u, 8u * (uint32_t)std::lround(scale * (0.5f * mc + 12.f) / 8.f)));
-		if (rounds == 2) chunk_ends_cut.assign({ec});
+		// two rounds, the first twice as long (opt.chunk_scale, opt.chunk_rounds).
+		const uint32_t ec = std::min(256u, std::max(24u, 8u * (uint32_t)std::lround(opt.chunk_scale * (0.5f * mc + 12.f) / 8.f)));
+		if (opt.chunk_rounds == 2) chunk_ends_cut.assign({ec});
 		else chunk_ends_cut.assign({ec, 2 * ec});
 	}
 	float last_keep_ratio = 1.f;
 	static constexpr float PROGRESSIVE_RATIO = 0.7f;
 	Dev<uint32_t> chunk_list, chunk_cnt;  // chunk_cnt: [k] round k's sample list length, [16] the long-ray list's, [32 + k] open rays
 	Dev<uint32_t> open_rays[2];          // the rays still open after a round (ping-pong: round k reads [(k - 1) & 1])
-	// spatial ray order of the progressive rounds (RaySort; NEUS_RAY_SORT=0: slot order, one-XCD-agnostic lists)
+	// spatial ray order of the progressive rounds (RaySort; without opt.ray_sort: slot order, one-XCD-agnostic lists)
 	Dev<uint32_t> rs_hist, rs_off, rs_perm;
 	Dev<uint16_t> rs_key;
-	bool ray_sort = [] { const char* e = std::getenv("NEUS_RAY_SORT"); return !(e && e[0] == '0'); }();
 	static constexpr uint32_t OPEN_CNT = 32;
 	static constexpr uint32_t RS_N_PERM = 48;  // chunk_cnt slot: the ray order's length (k_ray_sort_scan)
 	static constexpr uint32_t RAW_CNT = 49;    // chunk_cnt [49 + k]: rays open after round k, before the compaction cut (k = 0)
@@ -401,8 +386,7 @@ struct NeusTestbed {
 	// compaction base is already past the batch after a round. Training is bitwise the same; what changes is the summed
 	// composited count of such a step (a lower bound, still >= the batch), which with fixed rays feeds no result - only the
 	// logged loss scale, the chunk-end rule and the stats. So a step that the host reads back (a loss readback step, the last
-	// step of a train call) never cuts, and every value the host sees is the uncut one. NEUS_PROG_CUT=0 turns it off.
-	bool prog_cut = [] { const char* e = std::getenv("NEUS_PROG_CUT"); return !(e && e[0] == '0'); }();
+	// step of a train call) never cuts, and every value the host sees is the uncut one. Off without opt.prog_cut.
 	// With the spatial ray order, round 0 itself is split too: the sort puts the rays of the slots below the previous step's
 	// cut (+ 1/4, + 1024: cutw[CW_EST]) first (pass A); once pass A is scanned the cut is known whenever the prefix reaches
 	// the batch in those slots, and pass B (the rest of round 0) then has nothing to do.
@@ -413,7 +397,7 @@ struct NeusTestbed {
 	bool la_mcut = false;          // the pending lookahead's march was cut (march_cut_for)
 	bool cut_for(uint32_t step, bool progressive, bool last_in_call, bool dyn) const {
 		const uint32_t nch = (uint32_t)chunk_ends.size() + 1;
-		return prog_cut && progressive && cfg.fixed_rays_per_batch && !dyn && step % 16 != 0 && !last_in_call && nch >= 2 && nch <= 15;
+		return opt.prog_cut && progressive && cfg.fixed_rays_per_batch && !dyn && step % 16 != 0 && !last_in_call && nch >= 2 && nch <= 15;
 	}
 	// The march cut: on a cut step the compaction cut lies, nearly always, well inside the slots below the
 	// split estimate (cutw[CW_EST]: at the bench's step 800, 5.6 K of the 41 K kept slots), and no ray past it contributes a
@@ -427,17 +411,11 @@ struct NeusTestbed {
 	// the step before it in full when that one was cut, which makes its cap exact). The trained parameters are those of
 	// the full march in every case. A step the host reads back, one with (or before) an occupancy update, and the last two
 	// steps of a train call never cut the march, so the loss readback and the end of a call need no extra wait.
-	// NEUS_MARCH_CUT=0 turns it off.
-	bool march_cut_on = [] { const char* e = std::getenv("NEUS_MARCH_CUT"); return !(e && e[0] == '0'); }();
+	// Off without opt.march_cut.
 	bool force_full = false;      // the step being re-run marches every slot
-	// the occupancy-biased samples binned by their coarse cell before the density pass (NEUS_OCC_NU_SORT=1): bitwise the
-	// same grid, but 0.756-0.764 -> 0.765-0.771 ms/step at step 800 (profiles/r06occ_nu_sort_ab.txt: the binning's
-	// atomics on the few occupied bins cost more than the pass saves); off
-	bool occ_nu_sort = [] { const char* e = std::getenv("NEUS_OCC_NU_SORT"); return e && e[0] == '1'; }();
-	Dev<uint32_t> occ_nu_key, occ_nu_list, occ_nu_bins;
+	Dev<uint32_t> occ_nu_key, occ_nu_list, occ_nu_bins;  // opt.occ_nu_sort: the occupancy-biased samples binned by their coarse cell
 	bool abort_direct = false;            // the last risky step's word comes through abort_word (one rank)
 	volatile uint32_t* abort_word = nullptr;  // host-coherent pinned word k_loss_grad stores the witness to (one rank)
-	uint32_t mcut_div = [] { const char* e = std::getenv("NEUS_DBG_MARCH_CUT_DIV"); return e ? (uint32_t)std::max(1, std::atoi(e)) : 1u; }();  // test hook
 	bool mc_hist[2] = {false, false};  // the march of the last issued step / of the one before it was cut
 	struct StepSnap {
 		uint32_t training_step = 0, canonical_step = 0, adam_step = 0, call_left = 0;
@@ -453,7 +431,7 @@ struct NeusTestbed {
 	Dev<StepState> st_recount;
 	static bool occ_at(uint32_t cs) { const uint32_t n_prep = std::min(16u, std::max(1u, cs / 16u)); return cs % n_prep == 0; }
 	bool march_cut_for(uint32_t step, bool cut, uint32_t left_at_step) const {
-		if (!march_cut_on || force_full || !cut || profiling || !mwork.balanced || mwork.lanes_per_ray != 8 || ds.cone_angle != 0.0f) return false;
+		if (!opt.march_cut || force_full || !cut || profiling || !mwork.balanced || mwork.lanes_per_ray != 8 || ds.cone_angle != 0.0f) return false;
 		return (step + 1) % 16 != 0 && left_at_step >= 2 && !occ_at(step) && !occ_at(step + 1);
 	}
 	Dev<uint32_t> long_rays;  // the loss scan's wave-per-ray list (+ its counter in chunk_cnt[16])
@@ -492,7 +470,7 @@ struct NeusTestbed {
 	// accumulation of the later groups - on comm_stream (RCCL; one stream keeps every rank's collectives in one order),
 	// which the step's stream joins before the optimizer. Off (NEUS_EXCHANGE_OVERLAP=0, neus_testbed_set_exchange_overlap):
 	// one grouped exchange after the backward. Elementwise sums are the same either way (bitwise with two ranks).
-	bool exchange_overlap = true;
+	bool exchange_overlap = opt.exchange_overlap;
 	hipStream_t comm_stream = nullptr;
 	hipEvent_t ev_x[16] = {};
 	uint32_t ev_x_n = 0;
@@ -561,12 +539,11 @@ struct NeusTestbed {
 			// streams at the default priority, a testbed created after another one was destroyed ran the 16-level bench leg
 			// at 1.91 ms/step instead of 1.27 with the lookahead at the lowest priority (profiles/r05l16_priorities_ab.txt),
 			// presumably from how the runtime maps the streams onto its few hardware queues; explicit priorities on every
-			// stream keep it at 1.24. NEUS_MAIN_PRIO=0: the default priority.
-			const char* e = std::getenv("NEUS_MAIN_PRIO");
+			// stream keep it at 1.24. Without opt.main_prio: the default priority.
 			int lo = 0, hi = 0;
 			HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
 			main_prio = hi;
-			if (!(e && e[0] == '0')) {
+			if (opt.main_prio) {
 				HIP_CHECK(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, hi));
 				HIP_CHECK(hipStreamCreateWithPriority(&aux_stream, hipStreamNonBlocking, hi));
 			} else {
@@ -671,17 +648,6 @@ struct NeusTestbed {
 		launch_bitfield_linear(stream, bitfield.p, bf_lin.p);
 		occ_bbox.alloc(occ_bbox_scratch_floats());
 		launch_occ_bbox(stream, bitfield.p, occ_bbox.p);
-		{ const char* e = std::getenv("NEUS_RAY_CULL"); ray_cull = !(e && e[0] == '0'); }
-		{ const char* e = std::getenv("NEUS_EXCHANGE_OVERLAP"); exchange_overlap = !(e && e[0] == '0'); }
-		{ const char* e = std::getenv("NEUS_OCC_SORT"); occ_sort = !(e && e[0] == '0'); }
-		if (const char* e = std::getenv("NEUS_CHUNK_ENDS")) {
-			std::vector<uint32_t> v;
-			for (const char* p = e; *p;) { char* q = nullptr; const unsigned long x = std::strtoul(p, &q, 10); if (q == p) break; v.push_back((uint32_t)x); p = *q ? q + 1 : q; }
-			bool ok = !v.empty() && v.size() <= 14 && v[0] > 0;
-			for (size_t k = 1; k < v.size(); ++k) ok = ok && v[k] > v[k - 1];
-			if (ok) { chunk_ends = v; chunk_auto = false; chunk_ends_cut.clear(); }
-		}
-		{ const char* e = std::getenv("NEUS_SCATTER_NOSKIP"); scatter_noskip = e && e[0] == '1'; }
 		grid_mean.alloc(4); grid_partial.alloc(GRID3 / 1024);
 		HIP_CHECK(hipMemset(grid_mean.p, 0, 16));
 	}
@@ -820,22 +786,11 @@ struct NeusTestbed {
 		// binned grid-gradient scatter workspace (grid.hip)
 		swork = ScatterWork{};
 		swork.n_blocks = (batch + 255) / 256;
-		// wide-block binning: 512-sample workgroups (NEUS_SCATTER_CHUNK=1024: 1024-sample ones)
-		{
-			const char* e = std::getenv("NEUS_SCATTER_CHUNK");
-			swork.chunk = (e && std::string(e) == "1024") ? 1024u : (e && std::string(e) == "256") ? 256u : 512u;
-		}
+		// the path (per-block record regions unless opt.scatter_mode says otherwise) and its workgroups' samples
+		swork.mode = opt.scatter_mode;
+		swork.chunk = opt.scatter_chunk;
 		swork.n_chunks = (batch + swork.chunk - 1) / swork.chunk;
-		// per-block record regions (mode 2); NEUS_SCATTER=wide / binned select the wide-block (0) or the 256-sample (1)
-		// histogram / scan / bin paths (bitwise A/B references)
-		{
-			const char* e = std::getenv("NEUS_SCATTER");
-			swork.mode = !e ? 2u : std::string(e) == "binned" ? 1u : std::string(e) == "wide" ? 0u : 2u;
-			if (swork.mode != 2 && swork.chunk == 256) { swork.chunk = 512; swork.n_chunks = (batch + 511) / 512; }  // wide binning: 512 / 1024
-			// NEUS_SCATTER_LG=k: k workgroups per chunk each binning every k-th level (default: one per level)
-			const char* lg = std::getenv("NEUS_SCATTER_LG");
-			swork.level_groups = lg ? (uint32_t)std::max(0, std::atoi(lg)) : 0u;
-		}
+		swork.level_groups = opt.scatter_level_groups;
 		swork.n_buckets = scatter_n_buckets(gl);
 		if (swork.n_buckets > SB_MAX_BUCKETS) throw std::runtime_error("hash grid too large for the scatter buckets");
 		const size_t n_bins = (size_t)swork.n_buckets * swork.n_blocks + 1;
@@ -853,8 +808,7 @@ struct NeusTestbed {
 			sc_jobs2.alloc(jobs2.size());
 			HIP_CHECK(hipMemcpy(sc_jobs2.p, jobs2.data(), jobs2.size() * 4, hipMemcpyHostToDevice));
 			swork.jobs2 = (const uint4*)sc_jobs2.p; swork.n_jobs2 = (uint32_t)(jobs2.size() / 4);
-			swork.xcd_group = 4;
-			if (const char* e = std::getenv("NEUS_SC_XCD_GROUP")) swork.xcd_group = std::max(1u, (uint32_t)std::strtoul(e, nullptr, 10));
+			swork.xcd_group = opt.scatter_xcd_group;
 			if (sc_jobs2_before.size() > 17) throw std::runtime_error("region scatter: at most 16 levels");
 			for (size_t k = 0; k < sc_jobs2_before.size(); ++k) swork.jobs2_before[k] = sc_jobs2_before[k];
 			sc_rtab.alloc((size_t)l.L * swork.n_chunks * (SB_LEVEL_BUCKETS + 1));
@@ -885,8 +839,8 @@ struct NeusTestbed {
 		rays.alloc(6 * (size_t)MAX_RAYS); startt.alloc((size_t)MAX_RAYS);
 		march_rec.alloc((size_t)MAX_RAYS * NERF_STEPS); march_nrec.alloc(MAX_RAYS); march_queue.alloc(2);
 		march_seg.alloc((size_t)MAX_RAYS * MARCH_SEG_RECS);
-		mwork = MarchWork{march_rec.p, march_nrec.p, march_queue.p, march_waves(), march_seg.p, march_lanes(), jump_table()};
-		{ const char* e = std::getenv("NEUS_MARCH_BALANCE"); mwork.balanced = !(e && e[0] == '0') ? 1u : 0u; }
+		mwork = MarchWork{march_rec.p, march_nrec.p, march_queue.p, opt.march_waves, march_seg.p, opt.march_lanes, jump_table()};
+		mwork.balanced = opt.march_balance ? 1u : 0u;
 		nreq.alloc(MAX_RAYS); base.alloc(MAX_RAYS);
 		numsteps.alloc(2 * (size_t)MAX_RAYS); ccount.alloc(MAX_RAYS); cbase.alloc(MAX_RAYS);
 		l_sa.alloc(max_samples); l_ekt.alloc(max_samples); sample_ray.alloc(max_samples); cmap.alloc(batch);
@@ -1005,19 +959,6 @@ struct NeusTestbed {
 		adam_step = 0; lr_factor = 1.f;
 		HIP_CHECK(hipStreamSynchronize(stream));
 	}
-	// march waves launched (NEUS_MARCH_WAVES overrides). Default 0 = one lane per ray slot: the march is
-	// latency-bound (occupancy lookups), and measured on MI355X every wave fewer than the slots was slower
-	// (R = 2^18: 4096 waves 0.58 ms, 2048 0.75 ms, 1024 1.28 ms); the queue then only re-fills dropped slots.
-	uint32_t march_waves() const {
-		if (const char* e = std::getenv("NEUS_MARCH_WAVES")) return (uint32_t)std::strtoul(e, nullptr, 10);
-		return 0;
-	}
-	// lanes marching one ray (segments of its step sequence, see march.hip): 8 (NEUS_MARCH_LANES = 1 / 4 / 8).
-	// Measured on MI355X (Config S, R = 2^18, step 5): sampling 0.52 ms with 1 lane, 0.24 with 4, 0.21 with 8.
-	uint32_t march_lanes() const {
-		if (const char* e = std::getenv("NEUS_MARCH_LANES")) { const uint32_t v = (uint32_t)std::strtoul(e, nullptr, 10); return v == 1 || v == 4 || v == 16 ? v : 8u; }
-		return 8;
-	}
 	uint32_t gm_steps() const { return cfg.predict_global_movement ? cfg.global_movement_steps : 0u; }
 
 	void setup_mlp_ptrs() {
@@ -1082,7 +1023,7 @@ struct NeusTestbed {
 	ScatterWork scatter_work_for(float* g_grid, uint32_t valid, hipStream_t s) {
 		if (g_grid != grads.p + lay.grid_off || sc_jobs_before.empty()) return swork;
 		const uint32_t L = gl.n_levels, n_entries = gl.offset[L];
-		if (scatter_noskip) {  // A/B reference: the whole grid gradient zeroed before every scatter
+		if (opt.scatter_noskip) {  // A/B reference: the whole grid gradient zeroed before every scatter
 			HIP_CHECK(hipMemsetAsync(g_grid, 0, (size_t)n_entries * 2 * sizeof(float), s));
 			sc_zero_from = swork.n_buckets; sc_zero_from_e = n_entries;
 			return swork;
@@ -1243,14 +1184,14 @@ struct NeusTestbed {
 			// the uniform part in cell order (spatially coherent gathers; the max splat is order-independent): one cascade
 			// of cells or fewer uniform samples, so the uniform hash is a bijection onto the cells
 			const uint32_t u_lo = std::min(lo, n_uniform), u_hi = std::min(hi, n_uniform);
-			if (!exclusive && occ_sort && u_hi > u_lo && n_uniform <= GRID3) {
+			if (!exclusive && opt.occ_sort && u_hi > u_lo && n_uniform <= GRID3) {
 				if (!occ_ulist.p) occ_ulist.alloc(GRID3);
 				launch_occ_uniform_list(s, n_uniform, density_grid_ema_step, u_lo, u_hi, occ_ulist.p, scan_tmp.p);
 				os.ulist = occ_ulist.p; os.n_ulist = u_hi - u_lo;
-				// (occ_nu_sort: the occupancy-biased samples binned by their coarse cell as well; in index order the biased half
+				// (opt.occ_nu_sort: the occupancy-biased samples binned by their coarse cell as well; in index order the biased half
 				// takes 294 of the pass's 479 us, the cell-ordered uniform half 187 - profiles/r06occ_split.txt)
 				const uint32_t nu_lo = std::max(lo, n_uniform), n_nu_rank = hi > nu_lo ? hi - nu_lo : 0u;
-				if (occ_nu_sort && n_nu_rank) {
+				if (opt.occ_nu_sort && n_nu_rank) {
 					if (occ_nu_key.n < n_nu_rank) { occ_nu_key.alloc(n_nu_rank); occ_nu_list.alloc(n_nu_rank); }
 					occ_nu_bins.alloc(2 * 4096 * (size_t)(max_cascade + 1));
 					launch_occ_nu_list(s, n_nu_rank, nu_lo - n_uniform, os, occ_nu_key.p, occ_nu_bins.p, occ_nu_list.p, scan_tmp.p, scan_tmp_bytes);
@@ -1304,19 +1245,19 @@ struct NeusTestbed {
 		p.inv_loss_scale = 1.0f / p.loss_scale;
 		ensure_bias_table();
 		p.bias_tab = adam_bias.p; p.bias_converged = bias_conv ? 1u : 0u;
-		{ static const bool eager = [] { const char* e = std::getenv("NEUS_EAGER_EMA_H"); return e && e[0] == '1'; }(); p.skip_ema_h = eager ? 0u : 1u; }
+		p.skip_ema_h = opt.eager_ema_h ? 0u : 1u;
 		p.abort = &st.p->cut_abort;  // (the march cut's witness: a step that is re-run applies nothing)
 		return p;
 	}
-	// Adam in pieces beside the backward (adam_overlap; one rank, static scenes): the MLP blocks once the weight-gradient
+	// Adam in pieces beside the backward (opt.adam_overlap; static scenes): the MLP blocks once the weight-gradient
 	// reduction is done (beside the grid scatter), each grid level group once its accumulation launch is done (beside the
-	// next group's), on ad_stream; the step's stream joins it where the one Adam launch used to be. Elementwise, so the
-	// parameters are bitwise those of the one launch. Cut points are rounded down to 4 parameters (the kernel's 16-B
-	// groups): a range may start with the last few parameters of the level before it, whose gradient is final already.
-	bool adam_overlap = [] { const char* e = std::getenv("NEUS_ADAM_OVERLAP"); return e && e[0] == '1'; }();
+	// next group's), on ad_stream at one rank - the step's stream joins it where the one Adam launch used to be - and under
+	// data parallel on the exchange stream, each piece behind its range's all-reduce. Elementwise, so the parameters are
+	// bitwise those of the one launch. Cut points are rounded down to 4 parameters (the kernel's 16-B groups): a range may
+	// start with the last few parameters of the level before it, whose gradient is final already.
 	// ad_stream is the step's side stream (aux_stream, created with the step's stream at its priority): a stream of its own
 	// would be a fifth HIP stream of the process over GPU_MAX_HW_QUEUES = 4 hardware queues and share one - measured
-	// 1.12 -> 1.99 ms/step when it landed behind the lookahead's low-priority march (profiles/r06b_adam_overlap_ab.txt)
+	// 1.12 -> 1.99 ms/step when it landed behind the lookahead's low-priority march (profiles/r06b_adam_overlap_mlp_grid_ab.txt)
 	hipStream_t ad_stream = nullptr;
 	hipEvent_t ad_ev[8] = {}, ad_done = nullptr;
 	int ad_n = 0;
@@ -1631,7 +1572,7 @@ struct NeusTestbed {
 		if (abort_pending) check_abort();
 		train_step_body();
 	}
-	// The last issued step's march-cut witness (march_cut_on): when it aborted, its state changes were withheld on the
+	// The last issued step's march-cut witness (opt.march_cut): when it aborted, its state changes were withheld on the
 	// device; the host state goes back to its start and the step runs again with the full march.
 	void check_abort() {
 		abort_pending = false;
@@ -1670,7 +1611,7 @@ struct NeusTestbed {
 			st_recount.alloc(1);
 			HIP_CHECK(hipMemcpy(st_recount.p, &t, sizeof(t), hipMemcpyHostToDevice));
 			launch_march_count(stream, MAX_RAYS, max_samples, st_recount.p, DPInfo{rank, world}, ds, bitfield.p, bf_lin.p, s1.rng.state, s1.rng.inc,
-			                   rays.p, startt.p, nreq.p, mwork, nullptr, 0, ray_cull ? occ_bbox.p : nullptr);
+			                   rays.p, startt.p, nreq.p, mwork, nullptr, 0, opt.ray_cull ? occ_bbox.p : nullptr);
 			launch_march_write(stream, MAX_RAYS, st_recount.p, ds, rays.p, mwork, nreq.p, base.p, numsteps.p, coords.p, nullptr, max_samples,
 			                   scan_tmp.p, nullptr, 0);
 			HIP_CHECK(hipStreamSynchronize(stream));
@@ -1735,14 +1676,14 @@ struct NeusTestbed {
 		mark(1);
 		// progressive (cut-off-aware) inference this step: its round-0 list is written by the march
 		const bool progressive = progressive_mode == 2 || (progressive_mode == 1 && last_keep_ratio < PROGRESSIVE_RATIO);
-		const bool sorted_rays = progressive && ray_sort;  // round 0's list by k_ray_sort_place instead of the march write
+		const bool sorted_rays = progressive && opt.ray_sort;  // round 0's list by k_ray_sort_place instead of the march write
 		const RaySort rsort{rs_hist.p, rs_off.p, rs_key.p, rs_perm.p, chunk_cnt.p + RS_N_PERM};
 		if (la_have) {
 			if (canonical_step % n_prep == 0) throw std::runtime_error("train: lookahead issued before an occupancy update");
 			++la_steps;
-			if (la_stat && la_stat_used % 4 == 2) HIP_CHECK(hipEventRecord(la_stat_next(), s));
+			if (opt.la_stat && la_stat_used % 4 == 2) HIP_CHECK(hipEventRecord(la_stat_next(), s));
 			HIP_CHECK(hipStreamWaitEvent(s, ev_la_done, 0));  // this step's samples came from the previous step's lookahead
-			if (la_stat && la_stat_used % 4 == 3) HIP_CHECK(hipEventRecord(la_stat_next(), s));
+			if (opt.la_stat && la_stat_used % 4 == 3) HIP_CHECK(hipEventRecord(la_stat_next(), s));
 		}
 		const bool cut = la_have ? la_cut : cut_for(training_step, progressive, call_left == 0, dyn);
 		const std::vector<uint32_t>& ce = ends_for(cut);  // (a cut step's rounds: chunk_ends_cut)
@@ -1774,13 +1715,13 @@ struct NeusTestbed {
 			*abort_word = ~0u;
 			lp.abort_host = (uint32_t*)abort_word;
 		}
-		{ static const bool f = [] { const char* e = std::getenv("NEUS_DBG_LOSS_FENCE"); return e && e[0] == '1'; }(); lp.dbg_fence = f ? 1u : 0u; }
+		lp.dbg_fence = opt.dbg_loss_fence ? 1u : 0u;
 		const LossWork w = loss_work(base.p);
 		if (progressive) {
 			// rounds of per-ray chunks, each: network on the round's samples, alpha, the recurrence continued (march.hip);
 			// the "infer" phase mark then covers the composite as well
 			uint32_t e0 = 0;
-			// the compaction cut (prog_cut, cut_for): fixed rays per batch, not a step the host reads back (the loss readback
+			// the compaction cut (opt.prog_cut, cut_for): fixed rays per batch, not a step the host reads back (the loss readback
 			// steps, the last step of a train call), one rank's own batch
 			for (uint32_t k = 0; k < nch; ++k) {
 				const uint32_t e1 = k + 1 < nch ? ce[k] : 0xffffffffu;
@@ -1836,7 +1777,7 @@ struct NeusTestbed {
 		launch_exclusive_scan(s, scan_tmp.p, scan_tmp_bytes, ccount.p, cbase.p, MAX_RAYS);
 		launch_loss_ray(s, MAX_RAYS, st.p, dp, ds, lp, numsteps.p, ccount.p, cbase.p, w, loss.p, ek.p, mask.p);
 		launch_loss_grad(s, max_samples, st.p, dp, lp, coords.p, net_out.p, numsteps.p, w, coords_c.p, dL_dout.p);
-		if (dbg_loss_replay) {  // development (NEUS_DBG_LOSS_REPLAY=1): the same launch again, into separate outputs, and
+		if (opt.dbg_loss_replay) {  // development (NEUS_DBG_LOSS_REPLAY=1): the same launch again, into separate outputs, and
 			                     // copies of the loss-gradient kernel's inputs as they were right after it
 			dbg_co.alloc((size_t)batch * COORD_W); dbg_dl.alloc((size_t)batch * OUT_W);
 			launch_loss_grad(s, max_samples, st.p, dp, lp, coords.p, net_out.p, numsteps.p, w, dbg_co.p, dbg_dl.p);
@@ -1868,13 +1809,13 @@ struct NeusTestbed {
 			abort_pending = true;
 			abort_direct = !coll_on();
 		}
-		// ---- lookahead: the next step's ray sampling beside this step's backward (la_on; see the members)
+		// ---- lookahead: the next step's ray sampling beside this step's backward (opt.lookahead; see the members)
 		const bool get_loss = training_step % 16 == 0;
 		const StepCounterArgs sca{st.p, batch, max_samples, world, cfg.fixed_rays_per_batch, progressive ? chunk_cnt.p : nullptr, nch};
 		bool counters_done = false;
 		const uint32_t cs1 = training_step + 1;  // the next step's canonical step (static scenes)
 		const uint32_t n_prep1 = std::min(16u, std::max(1u, cs1 / 16u));
-		const bool la_go = la_on && la_next_in_call && !dyn && !use_delta && !profiling && !dbg_loss_replay &&
+		const bool la_go = opt.lookahead && la_next_in_call && !dyn && !use_delta && !profiling && !opt.dbg_loss_replay &&
 		                   !dbg_lds_fill && g_dbg_lds_fill == 0 && g_dbg_xcd_shift == 0 && cs1 % 16 != 0 && cs1 % n_prep1 != 0 &&
 		                   !(get_loss && loss_pending);
 		// with a group, the all-reduced word goes to the host from the step counters' launch that the lookahead puts right
@@ -1914,17 +1855,15 @@ struct NeusTestbed {
 				if (!la_stream) {
 					// the lookahead stream at the lowest priority: the backward's workgroups are dispatched first and the march's
 					// fill what they leave (1.154 -> 1.107 ms/step at the bench state; the default priority 1.139, the highest
-					// 1.141: profiles/r05lap_lookahead_priority_ab.txt). NEUS_LA_PRIO: -1 lowest, 0 default, 1 highest.
-					const char* e = std::getenv("NEUS_LA_PRIO");
-					const int want = e ? std::atoi(e) : -1;
+					// 1.141: profiles/r05lap_lookahead_priority_ab.txt). opt.la_prio: -1 lowest, 0 default, 1 highest.
+					const int want = opt.la_prio;
 					int lo = 0, hi = 0;
 					HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));  // (lo: least urgent, hi: most urgent; hi <= lo numerically)
 					if (want == 0) HIP_CHECK(hipStreamCreateWithFlags(&la_stream, hipStreamNonBlocking));
 					else HIP_CHECK(hipStreamCreateWithPriority(&la_stream, hipStreamNonBlocking, want > 0 ? hi : lo));
 					// (device-side hand-offs between the step's and the lookahead's kernels: no system-scope fence - its
-					// L2 write-back held the step's stream ~6 us at the record; NEUS_EV_SYSFENCE=1 keeps it, for A/B)
-					const char* f = std::getenv("NEUS_EV_SYSFENCE");
-					const unsigned fl = hipEventDisableTiming | (f && f[0] == '1' ? 0u : hipEventDisableSystemFence);
+					// L2 write-back held the step's stream ~6 us at the record; opt.ev_sysfence keeps it, for A/B)
+					const unsigned fl = hipEventDisableTiming | (opt.ev_sysfence ? 0u : hipEventDisableSystemFence);
 					HIP_CHECK(hipEventCreateWithFlags(&ev_la_start, fl));
 					HIP_CHECK(hipEventCreateWithFlags(&ev_la_done, fl));
 				}
@@ -1936,15 +1875,15 @@ struct NeusTestbed {
 				r1.advance();
 				const bool prog1 = progressive_mode == 2 || (progressive_mode == 1 && last_keep_ratio < PROGRESSIVE_RATIO);
 				la_cut = cut_for(training_step + 1, prog1, call_left <= 1, false);
-				la_mcut = march_cut_for(training_step + 1, la_cut && ray_sort, call_left - 1);
+				la_mcut = march_cut_for(training_step + 1, la_cut && opt.ray_sort, call_left - 1);
 				const bool cut1 = la_cut, mcut1 = la_mcut;
-				la_at = mcut1 ? la_at_cut : la_at_full;
+				la_at = mcut1 ? opt.la_at_cut : opt.la_at_full;
 				la_deferred = [this, cs, dp, r1, prog1, cut1, mcut1] {
 					HIP_CHECK(hipEventRecord(ev_la_start, cs));
 					HIP_CHECK(hipStreamWaitEvent(la_stream, ev_la_start, 0));
-					if (la_stat) { la_stat_used -= la_stat_used % 4; HIP_CHECK(hipEventRecord(la_stat_next(), la_stream)); }
+					if (opt.la_stat) { la_stat_used -= la_stat_used % 4; HIP_CHECK(hipEventRecord(la_stat_next(), la_stream)); }
 					issue_march(la_stream, dp, r1, prog1, scan_tmp_la.p, cut1, mcut1);
-					if (la_stat) HIP_CHECK(hipEventRecord(la_stat_next(), la_stream));
+					if (opt.la_stat) HIP_CHECK(hipEventRecord(la_stat_next(), la_stream));
 					HIP_CHECK(hipEventRecord(ev_la_done, la_stream));
 				};
 				if (cs != s) la_fire(0x7fffffff);  // (the communication stream: issued now, before the gradients' collectives queue there)
@@ -1959,10 +1898,10 @@ struct NeusTestbed {
 		// entry by k_scatter_accum, zeros with no samples); the global-movement phase skips it: zero the buffer there
 		if (!(!dyn || train_canonical)) HIP_CHECK(hipMemsetAsync(grads.p, 0, (size_t)lay.P * 4, s));
 		mark(4);
-		// the overlapped exchange (xo): the canonical backward all-reduces its gradient ranges as they finish; adam_overlap
-		// (one rank, static scenes): the optimizer step in pieces beside the scatter
+		// the overlapped exchange (xo): the canonical backward all-reduces its gradient ranges as they finish; opt.adam_overlap
+		// (static scenes; one rank, or behind the overlapped exchange): the optimizer step in pieces beside the scatter
 		AdamSplit asp{};
-		const bool a_over = adam_overlap && !dyn && (!coll_on() || xo);
+		const bool a_over = opt.adam_overlap && !dyn && (!coll_on() || xo);
 		if (a_over) asp.p = adam_params();
 		if (use_delta) {
 			// the training forward runs on the deformed batch; dL/d(position) feeds the DeltaNetwork backward
@@ -2061,12 +2000,12 @@ struct NeusTestbed {
 		const std::vector<uint32_t>& ce = ends_for(cut);
 		const uint32_t nch = (uint32_t)ce.size() + 1;
 		const Round0List r0{ce[0], cbase.p, chunk_list.p, chunk_cnt.p, nch + 1};
-		const bool sorted_rays = progressive && ray_sort;
+		const bool sorted_rays = progressive && opt.ray_sort;
 		MarchWork mw = mwork;
 		if (mcut) mw.est_cut = cutw.p + CW_EST;  // (the split sort's estimate: pass A's slots are the marched ones)
-		mw.est_div = mcut_div;
+		mw.est_div = opt.march_cut_div;
 		launch_march_count(s, MAX_RAYS, max_samples, st.p, dp, ds, bitfield.p, bf_lin.p, r.state, r.inc, rays.p, startt.p, nreq.p, mw,
-		                   progressive ? chunk_cnt.p : nullptr, RAW_CNT + nch, ray_cull ? occ_bbox.p : nullptr);  // list lengths + open-ray counts
+		                   progressive ? chunk_cnt.p : nullptr, RAW_CNT + nch, opt.ray_cull ? occ_bbox.p : nullptr);  // list lengths + open-ray counts
 		launch_march_write(s, MAX_RAYS, st.p, ds, rays.p, mw, nreq.p, base.p, numsteps.p, coords.p, nullptr, max_samples, scan,
 		                   progressive && !sorted_rays ? &r0 : nullptr, dbg_lds_fill);
 		const RaySort rsort{rs_hist.p, rs_off.p, rs_key.p, rs_perm.p, chunk_cnt.p + RS_N_PERM};
@@ -2174,6 +2113,7 @@ int neus_device_synchronize(void) { return guard([&] { HIP_CHECK(hipDeviceSynchr
 int neus_testbed_create(int device, NeusTestbed** out) {
 	return guard([&] {
 		g_alloc_base = g_alloc_seq.load();
+		g_alloc_dbg = alloc_debug_from_env();
 		*out = new NeusTestbed(device);
 	});
 }
@@ -2200,7 +2140,7 @@ int neus_testbed_train(NeusTestbed* tb, uint32_t n_steps) {
 		// the pattern alternates with its complement from step to step
 		struct FillScope { ~FillScope() { g_dbg_lds_fill = 0; g_dbg_xcd_shift = 0; } } fill_scope;
 		// (a lookahead left pending by a step that threw is dropped: the next step marches again, the same samples)
-		struct LaScope { NeusTestbed* t; ~LaScope() { if (t->la_pending) { (void)hipStreamSynchronize(t->la_stream); t->la_pending = false; } t->la_next_in_call = false; if (t->la_stat) t->la_stat_report(); } } la_scope{tb};
+		struct LaScope { NeusTestbed* t; ~LaScope() { if (t->la_pending) { (void)hipStreamSynchronize(t->la_stream); t->la_pending = false; } t->la_next_in_call = false; if (t->opt.la_stat) t->la_stat_report(); } } la_scope{tb};
 		for (uint32_t i = 0; i < n_steps; ++i) {
 			g_dbg_lds_fill = tb->dbg_lds_fill_all ? ((tb->training_step & 1) ? ~tb->dbg_lds_fill_all : tb->dbg_lds_fill_all) : 0u;
 			g_dbg_xcd_shift = tb->dbg_xcd_shift;
@@ -2608,7 +2548,7 @@ static void time_kernel_impl(NeusTestbed* tb, int kernel, int variant, int iters
 		const uint32_t* lin = t.bf_lin.p;
 		auto march = [&]() {
 			launch_march_count(s, MAX_RAYS, t.max_samples, t.st.p, dp, t.ds, t.bitfield.p, lin, t.rng.state, t.rng.inc, t.rays.p, t.startt.p, t.nreq.p, t.mwork,
-			                   nullptr, 0, t.ray_cull ? t.occ_bbox.p : nullptr);
+			                   nullptr, 0, t.opt.ray_cull ? t.occ_bbox.p : nullptr);
 			launch_march_write(s, MAX_RAYS, t.st.p, t.ds, t.rays.p, t.mwork, t.nreq.p, t.base.p, t.numsteps.p, t.coords.p,
 			                   t.sample_ray.p, t.max_samples, t.scan_tmp.p);
 		};
@@ -2627,7 +2567,7 @@ static void time_kernel_impl(NeusTestbed* tb, int kernel, int variant, int iters
 			if (variant != 98 || k == 0) HIP_CHECK(hipEventRecord(evs[k], s));
 			switch (kernel) {
 			case 0: launch_march_count(s, MAX_RAYS, t.max_samples, t.st.p, dp, t.ds, t.bitfield.p, lin, t.rng.state, t.rng.inc, t.rays.p, t.startt.p, t.nreq.p, t.mwork,
-			                   nullptr, 0, t.ray_cull ? t.occ_bbox.p : nullptr); break;
+			                   nullptr, 0, t.opt.ray_cull ? t.occ_bbox.p : nullptr); break;
 			case 1: launch_march_write(s, MAX_RAYS, t.st.p, t.ds, t.rays.p, t.mwork, t.nreq.p, t.base.p, t.numsteps.p,
 			                           t.coords.p, t.sample_ray.p, t.max_samples, t.scan_tmp.p); break;
 			case 2: debug_launch_loss_scan(s, variant, MAX_RAYS, t.numsteps.p, w, t.ccount.p); break;
@@ -2685,7 +2625,7 @@ static void time_kernel_impl(NeusTestbed* tb, int kernel, int variant, int iters
 				MarchWork mw = t.mwork;
 				mw.est_cut = t.cutw.p + CW_EST;
 				launch_march_count(s, MAX_RAYS, t.max_samples, t.st.p, dp, t.ds, t.bitfield.p, lin, t.rng.state, t.rng.inc, t.rays.p, t.startt.p, t.nreq.p,
-				                   mw, nullptr, 0, t.ray_cull ? t.occ_bbox.p : nullptr);
+				                   mw, nullptr, 0, t.opt.ray_cull ? t.occ_bbox.p : nullptr);
 				break;
 			}
 			default: throw std::runtime_error("unknown kernel id");
@@ -2777,9 +2717,9 @@ int neus_debug_march_profile(NeusTestbed* tb, unsigned long long* out, uint32_t 
 		HIP_CHECK(hipMemsetAsync(buf.p, 0, (size_t)waves * 64, s));
 		MarchWork mw = t.mwork;
 		mw.prof = buf.p;
-		if (const char* e = std::getenv("NEUS_MARCH_DBG")) mw.dbg = (uint32_t)std::strtoul(e, nullptr, 10);
+		mw.dbg = t.opt.march_dbg;
 		launch_march_count(s, MAX_RAYS, t.max_samples, t.st.p, DPInfo{t.rank, t.world}, t.ds, t.bitfield.p, t.bf_lin.p, t.rng.state, t.rng.inc,
-		                   t.rays.p, t.startt.p, t.nreq.p, mw, nullptr, 0, t.ray_cull ? t.occ_bbox.p : nullptr);
+		                   t.rays.p, t.startt.p, t.nreq.p, mw, nullptr, 0, t.opt.ray_cull ? t.occ_bbox.p : nullptr);
 		HIP_CHECK(hipStreamSynchronize(s));
 		const uint32_t n = std::min(waves, max_waves);
 		HIP_CHECK(hipMemcpy(out, buf.p, (size_t)n * 64, hipMemcpyDeviceToHost));
@@ -3157,7 +3097,7 @@ static void sample_rays_impl(NeusTestbed* tb, void* stream, uint32_t n_rays, uin
 		if (list) { c0.alloc(n_rays); cnt.alloc(2); }
 		const Round0List r0{e1, c0.p, list, cnt.p, 2u};
 		launch_march_count(s, n_rays, max_samples, sst.p, DPInfo{rank, world}, tb->ds, bitfield, lin.p, rng_state, rng_inc, rays, st_t.p, nr.p, mw,
-		                   list ? cnt.p : nullptr, list ? 2u : 0u, tb->ray_cull ? bb.p : nullptr);
+		                   list ? cnt.p : nullptr, list ? 2u : 0u, tb->opt.ray_cull ? bb.p : nullptr);
 		Dev<uint32_t> sr; sr.alloc(std::max<uint32_t>(1, max_samples));
 		launch_march_write(s, n_rays, sst.p, tb->ds, rays, mw, nr.p, bs.p, numsteps, coords, sr.p, max_samples, tmp.p, list ? &r0 : nullptr, lds_fill);
 		HIP_CHECK(hipMemcpyAsync(&h, sst.p, sizeof(h), hipMemcpyDeviceToHost, s));

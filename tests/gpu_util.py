@@ -1,4 +1,5 @@
 """Device-buffer plumbing for the GPU parity tests (torch only allocates and copies)."""
+import contextlib
 import ctypes as C
 import os
 
@@ -44,27 +45,35 @@ def ptr(x):
     return C.c_void_p(x.data_ptr() if x is not None else 0)
 
 
-def scatter_testbed(sc, mode, batch):
-    """A base.json testbed on scene sc in one of the grid-gradient scatter modes: "regions" (per-block record regions,
-    512-sample workgroups: the default), "regions1024" (1024-sample ones), "seg" (wide-block binning, 512), "seg1024" or
-    "binned" (the 256-sample histogram / scan / bin path)."""
-    from neus2_amd import pyngp
-    env = {"NEUS_SCATTER": {"binned": "binned", "seg": "wide", "seg1024": "wide"}.get(mode),
-           "NEUS_SCATTER_CHUNK": "1024" if mode.endswith("1024") else None}
-    old = {k: os.environ.get(k) for k in env}
-    for k, v in env.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = v
+@contextlib.contextmanager
+def env(**kv):
+    """The environment variables kv set (a None value: removed) inside the block, their previous values restored on every
+    exit path. A testbed reads its NEUS_* switches when it is created: the block covers the creation, and by habit the
+    dataset and the network load as well."""
+    old = {k: os.environ.get(k) for k in kv}
     try:
-        tb = pyngp.Testbed(pyngp.TestbedMode.Nerf)
-        tb.set_dataset(sc["images"], sc["focal"], sc["principal"], sc["xforms"], 1)
-        tb.reload_network_from_file(os.path.join(ROOT, "configs", "nerf", "base.json"), batch_size=batch)
+        for k, v in kv.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = str(v)
+        yield
     finally:
         for k, v in old.items():
             if v is None:
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+
+
+def scatter_testbed(sc, mode, batch):
+    """A base.json testbed on scene sc in one of the grid-gradient scatter modes: "regions" (per-block record regions,
+    512-sample workgroups: the default), "regions1024" (1024-sample ones), "seg" (wide-block binning, 512), "seg1024" or
+    "binned" (the 256-sample histogram / scan / bin path)."""
+    from neus2_amd import pyngp
+    with env(NEUS_SCATTER={"binned": "binned", "seg": "wide", "seg1024": "wide"}.get(mode),
+             NEUS_SCATTER_CHUNK="1024" if mode.endswith("1024") else None):
+        tb = pyngp.Testbed(pyngp.TestbedMode.Nerf)
+        tb.set_dataset(sc["images"], sc["focal"], sc["principal"], sc["xforms"], 1)
+        tb.reload_network_from_file(os.path.join(ROOT, "configs", "nerf", "base.json"), batch_size=batch)
     return tb

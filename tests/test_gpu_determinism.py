@@ -23,6 +23,8 @@ import threading
 import numpy as np
 import pytest
 
+from gpu_util import env
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -98,8 +100,7 @@ def test_lookahead_sampling_bitwise(torch_cuda):
     sc = scenes.sphere_scene(16, 400, 300, principal=(0.51, 0.52))
     out = {}
     for la in ("0", "1"):
-        os.environ["NEUS_LOOKAHEAD"] = la
-        try:
+        with env(NEUS_LOOKAHEAD=la):
             tb = pyngp.Testbed(pyngp.TestbedMode.Nerf)
             tb.set_dataset(sc["images"], sc["focal"], sc["principal"], sc["xforms"], 1)
             tb.reload_network_from_file(os.path.join(ROOT, "configs", "nerf", "base.json"), batch_size=1 << 16)
@@ -108,8 +109,6 @@ def test_lookahead_sampling_bitwise(torch_cuda):
             out[la] = {"params": tb.get_params(), "ema": tb.get_ema_params(), "grid": grid, "bitfield": bf,
                        "counts": np.concatenate(tb.ray_counts(1 << 16)[:2]), "step": tb.stats()["training_step"]}
             del tb
-        finally:
-            os.environ.pop("NEUS_LOOKAHEAD", None)
     assert out["0"]["step"] == out["1"]["step"] == 300
     for k in ("params", "ema", "grid", "bitfield", "counts"):
         np.testing.assert_array_equal(out["0"][k], out["1"][k], err_msg=k)

@@ -7,7 +7,6 @@
   witness and the host's re-run of a step whose witness failed).
 Each is compared bitwise with the same training without it. Reference: testbed_nerf.cu:3723-4001 (the step),
 adam.h:51-160 (elementwise Adam)."""
-import contextlib
 import os
 import sys
 import threading
@@ -15,26 +14,14 @@ import threading
 import numpy as np
 import pytest
 
+from gpu_util import env as _env
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 BATCH = 4096
-
-
-@contextlib.contextmanager
-def _env(**kv):
-    old = {k: os.environ.get(k) for k in kv}
-    os.environ.update({k: str(v) for k, v in kv.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _testbed(sc, fixed_rays=0, batch=BATCH):

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from gpu_util import dev, host, ptr
+from gpu_util import dev, host, ptr, env as _env
 
 pytestmark = pytest.mark.gpu
 
@@ -946,14 +946,11 @@ def test_multilane_march_equals_single_lane(env):
     sc = env["sc"]
     tbs = {}
     for key, lanes, bal in (("1", "1", "1"), ("4", "4", "1"), ("8", "8", "1"), ("8u", "8", "0"), ("16", "16", "1")):
-        os.environ["NEUS_MARCH_LANES"] = lanes
-        os.environ["NEUS_MARCH_BALANCE"] = bal
-        tb = pyngp.Testbed(pyngp.TestbedMode.Nerf)
-        tb.set_dataset(sc["images"], sc["focal"], sc["principal"], sc["xforms"], 1)
-        tb.reload_network_from_file(os.path.join(ROOT, "configs", "nerf", "base.json"), batch_size=BATCH)
+        with _env(NEUS_MARCH_LANES=lanes, NEUS_MARCH_BALANCE=bal):
+            tb = pyngp.Testbed(pyngp.TestbedMode.Nerf)
+            tb.set_dataset(sc["images"], sc["focal"], sc["principal"], sc["xforms"], 1)
+            tb.reload_network_from_file(os.path.join(ROOT, "configs", "nerf", "base.json"), batch_size=BATCH)
         tbs[key] = tb
-    os.environ.pop("NEUS_MARCH_LANES", None)
-    os.environ.pop("NEUS_MARCH_BALANCE", None)
     rng = np.random.default_rng(17)
     n_rays, max_s = 8192, 8192 * 64
     bfs = [_bitfield(env)]

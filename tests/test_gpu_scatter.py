@@ -10,7 +10,7 @@ import os
 import numpy as np
 import pytest
 
-from gpu_util import dev, ptr, scatter_testbed as _testbed
+from gpu_util import dev, env, ptr, scatter_testbed as _testbed
 
 pytestmark = pytest.mark.gpu
 
@@ -81,20 +81,10 @@ def test_valid_level_drop_matches_zeroed_reference(scene, torch_cuda, tmp_path):
     from neus2_amd import pyngp
     out = []
     for noskip in (False, True):
-        old = os.environ.get("NEUS_SCATTER_NOSKIP")
-        if noskip:
-            os.environ["NEUS_SCATTER_NOSKIP"] = "1"
-        else:
-            os.environ.pop("NEUS_SCATTER_NOSKIP", None)
-        try:
+        with env(NEUS_SCATTER_NOSKIP="1" if noskip else None):
             tb = pyngp.Testbed(pyngp.TestbedMode.Nerf)
             tb.set_dataset(scene["images"], scene["focal"], scene["principal"], scene["xforms"], 1)
             tb.reload_network_from_file(os.path.join(ROOT, "configs", "nerf", "base.json"), batch_size=4096)
-        finally:
-            if old is None:
-                os.environ.pop("NEUS_SCATTER_NOSKIP", None)
-            else:
-                os.environ["NEUS_SCATTER_NOSKIP"] = old
         tb.train_steps(20)
         snap = str(tmp_path / f"early_{int(noskip)}.msgpack")
         tb.save_snapshot(snap, include_optimizer_state=True)
