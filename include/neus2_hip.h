@@ -163,9 +163,10 @@ typedef struct NeusNetLayout {
  * became tcnn's create_network(n_input_dims, n_output_dims, network), the NerfNetwork factory neus_module_create_nerf_network;
  * version 3: NeusDataParallelInfo gained host_group; version 4: neus_module_create_encoding gained requested_precision;
  * version 5: neus_testbed_{set_,}exchange_timing, neus_host_group_create gained job_token; version 6: NeusTrainStats gained
- * march_cut_steps and march_cut_reruns).
+ * march_cut_steps and march_cut_reruns; version 7: neus_module_backward_backward_input writes dL_ddLdoutput and dL_dinput for
+ * every module kind (the network modules ignored both pointers before).
  * Bindings compare it on load so that a stale library or binding fails loudly instead of misreading arguments. */
-#define NEUS_ABI_VERSION 6u
+#define NEUS_ABI_VERSION 7u
 int neus_abi_version(uint32_t* out);
 const char* neus_last_error(void);
 int neus_device_count(int* count);
@@ -481,8 +482,15 @@ int neus_debug_host_group_allreduce(NeusHostGroup* group, void* host, uint64_t n
  *                                needs n % 128 == 0 and includes the eikonal second order (as nerf_network.h:330-601); its
  *                                dL_dinput ([n][7] f32) carries the position columns (dt / direction columns written 0).
  * Parameter gradients dL_dparams are param precision (fp16, tcnn's trainer.h:72-109) unless the config sets
- * "gradient_precision": "fp32". backward_backward_input is the encoding's (grid.h:1697-1800, without the dL_dinput term),
- * the network-with-input-encoding's and create_network's (fully_fused_mlp.cu:1088-1198: parameter gradients only).
+ * "gradient_precision": "fp32". backward_backward_input is complete for the encoding (grid.h:1697-1800, dL_dinput as
+ * kernel_grid_backward_input_backward_input, grid.h:1010-1181), the network-with-input-encoding and create_network: with
+ * S = dL_ddLdinput . dL/dinput (dL/dinput the first backward's result for dL_doutput) it writes, each only when its pointer is
+ * non-null, dL_dparams = dS/dparams (by gradient_mode), dL_ddLdoutput = dS/d(dL_doutput) (the output's shape and precision; the
+ * encoding's in its output layout) and dL_dinput = dS/dinput ([n][n_input_dims] f32, overwritten; a sample's levels are summed in
+ * level order without atomics, so two calls agree bitwise; all zeros for create_network, whose first derivative is piecewise
+ * constant). The network chains carry no second derivative of an activation: dL_ddLdoutput and dL_dinput are exact, and
+ * accepted, only for hidden activation ReLU or None with output activation None (ReLU'' = 0); for any other network a non-null
+ * dL_ddLdoutput or dL_dinput is an error and the parameter gradients (both pointers null) stay available.
  * Progressive levels follow set_training_step (grid.h:2427-2437; 0 = all levels). */
 typedef struct NeusModule NeusModule;
 typedef struct NeusContext NeusContext;
@@ -507,8 +515,9 @@ int neus_module_create_encoding(uint32_t n_input_dims, const char* encoding_json
  * (NetworkWithInputEncoding: network first, network_with_input_encoding.h:262-270), the MLP's input width DE = 2 n_levels
  * padded to 16 with zeros (grid.h:1540-1550). HashGrid -> 1 hidden ReLU layer of 16 / 64 neurons -> linear output of <= 16
  * dims runs as one fused kernel; other shapes as the grid kernels feeding the FullyFusedMLP layers. backward_backward_input
- * follows network_with_input_encoding.h:159-250 / fully_fused_mlp.cu:1088-1198 (parameter gradients only; dL_ddLdoutput and
- * dL_dinput are not written, as in the reference). */
+ * follows network_with_input_encoding.h:159-250 / fully_fused_mlp.cu:1088-1198: parameter gradients, dL_ddLdoutput = J_mlp J_enc
+ * dL_ddLdinput as [n][padded n_output_dims] fp16 and dL_dinput = the HashGrid's second derivative in x of dL/d(encoding) (see
+ * above for the activations these two are provided for). */
 int neus_module_create_network_with_input_encoding(uint32_t n_input_dims, uint32_t n_output_dims, const char* encoding_json,
                                                    const char* network_json, uint32_t batch_capacity, NeusModule** out);
 int neus_module_destroy(NeusModule* m);

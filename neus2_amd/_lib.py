@@ -133,7 +133,7 @@ EXPORTS = [
 ]
 
 # include/neus2_hip.h's NEUS_ABI_VERSION this binding was written against: a library of another ABI fails to load
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _lib = None
 

@@ -760,6 +760,46 @@ __global__ void __launch_bounds__(256) k_enc_ddLdoutput(uint32_t n, uint32_t ld,
 	}
 }
 
+// dL_dinput of backward_backward_input (kernel_grid_backward_input_backward_input, grid.h:1010-1181): d/dx of
+// u . dL/dx with u = dL_ddLdinput [n][3] f32 and g = dL_dy paired [L][ld] half2. Level-major like k_grid_encode
+// (blockIdx.y = level: the same 8 gathers per sample and level, the level's table resident in L2 while its blocks run);
+// each (level, sample) writes its three terms to partial [3 l + d][n] and k_grid_ddx_sum adds a sample's levels in
+// level order, so the result has no atomics and is bitwise repeatable. Only the levels <= valid_level are launched.
+__global__ void __launch_bounds__(256) k_grid_ddx(uint32_t n, uint32_t ld, const float* __restrict__ coords, const GridLevels gl,
+                                                  const half_t* __restrict__ grid, const uint32_t* __restrict__ g, const float* __restrict__ ddx,
+                                                  float* __restrict__ partial) {
+	const uint32_t l = blockIdx.y;
+	const half_t* gp = grid + (size_t)gl.offset[l] * 2;
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+		const float* c = coords + (size_t)i * 3;
+		const LevelSetup s = level_setup(gl, l, c[0], c[1], c[2]);
+		h2 v[8];
+		gather_corners(s, gp, v);
+		const uint32_t a = g[(size_t)l * ld + i];
+		const h2 gl2 = *(const h2*)&a;
+		const float g0 = (float)gl2[0], g1 = (float)gl2[1];
+		float t[8];
+#pragma unroll
+		for (int k = 0; k < 8; ++k) t[k] = __builtin_fmaf((float)v[k][0], g0, (float)v[k][1] * g1);
+		const float u[3] = {ddx[(size_t)i * 3], ddx[(size_t)i * 3 + 1], ddx[(size_t)i * 3 + 2]};
+		float r[3];
+		level_ddx(s, t, u, r);
+#pragma unroll
+		for (int d = 0; d < 3; ++d) partial[(size_t)(3 * l + d) * n + i] = r[d];
+	}
+}
+// out[i][d] = sum over l < n_active, in level order, of partial[3 l + d][i] (n_active = 0: zeros)
+__global__ void __launch_bounds__(256) k_grid_ddx_sum(uint32_t n, uint32_t n_active, const float* __restrict__ partial, float* __restrict__ out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	float r[3] = {0.f, 0.f, 0.f};
+	for (uint32_t l = 0; l < n_active; ++l)
+#pragma unroll
+		for (int d = 0; d < 3; ++d) r[d] += partial[(size_t)(3 * l + d) * n + i];
+#pragma unroll
+	for (int d = 0; d < 3; ++d) out[(size_t)i * 3 + d] = r[d];
+}
+
 // Encoding output layouts of the operator module (tcnn GPUMatrix layouts): paired [L][n] half2 (this build's kernels)
 // <-> AoS [n][2L] (column-major: the cpp::Module view, cpp_api.cu:58-70) or SoA [2L][n] (GridEncoding's preferred
 // layout, grid.h:2357-2359). One thread per (sample, level).
@@ -829,6 +869,18 @@ void launch_enc_input_grad(hipStream_t s, uint32_t n, uint32_t ld, uint32_t L, c
 }
 void launch_enc_ddLdoutput(hipStream_t s, uint32_t n, uint32_t ld, uint32_t L, const float* ddx, const float* dydx, half_t* out, float4* v4) {
 	if (n) k_enc_ddLdoutput<<<(n + 255) / 256, 256, 0, s>>>(n, ld, L, ddx, dydx, (uint32_t*)out, v4);
+}
+uint32_t grid_ddx_active_levels(const GridLevels& gl, uint32_t valid_level) { return valid_level >= gl.n_levels ? gl.n_levels : valid_level + 1; }
+void launch_grid_ddx_sum(hipStream_t s, uint32_t n, uint32_t n_active, const float* partial, float* dLdx) {
+	if (n) k_grid_ddx_sum<<<(n + 255) / 256, 256, 0, s>>>(n, n_active, partial, dLdx);
+}
+void launch_grid_ddx(hipStream_t s, uint32_t n, uint32_t ld, const float* coords, const GridLevels& gl, uint32_t valid_level, const half_t* grid,
+                     const half_t* g, const float* ddx, float* partial, float* dLdx) {
+	if (!n) return;
+	const uint32_t na = grid_ddx_active_levels(gl, valid_level);
+	const uint32_t gx = std::min<uint32_t>((n + 255) / 256, 4096);
+	if (na) k_grid_ddx<<<dim3(gx, na), 256, 0, s>>>(n, ld, coords, gl, grid, (const uint32_t*)g, ddx, partial);
+	launch_grid_ddx_sum(s, n, na, partial, dLdx);
 }
 void launch_grid_encode(hipStream_t s, const uint32_t* n_ptr, uint32_t n_fixed, uint32_t ld, const float* coords, uint32_t coord_stride,
                         const GridLevels& gl, uint32_t valid_level, const half_t* grid, uint32_t* enc, float* dydx, uint32_t grid_x,

@@ -77,4 +77,29 @@ __device__ __forceinline__ void interp_dydx(const LevelSetup& s, const h2 v[8], 
 	}
 }
 
+// One level's term of d/dx (u . dL/dx), the dL_dinput of backward_backward_input (kernel_grid_backward_input_backward_input,
+// grid.h:1010-1181, linear interpolation): with t[c] = T[corner c] . dL_dy of the level,
+//   r[j] = scale^2 sum_{i != j} u[i] sum_c sigma_ci sigma_cj w_ck t[c]
+// (sigma_cd = +-1 by corner bit d, k the axis that is neither i nor j, w_ck its interpolation weight; the i = j terms are
+// zero because the weights are linear in each axis). The mixed term of a pair (i, j) serves r[i] and r[j].
+__device__ __forceinline__ void level_ddx(const LevelSetup& s, const float t[8], const float u[3], float r[3]) {
+	r[0] = r[1] = r[2] = 0.f;
+#pragma unroll
+	for (int k = 0; k < 3; ++k) {
+		const int i = k == 0 ? 1 : 0, j = k == 2 ? 1 : 2;
+		float m = 0.f;
+#pragma unroll
+		for (uint32_t c = 0; c < 8; ++c) {
+			const float w = (c & (1u << k)) ? s.pos[k] : 1.f - s.pos[k];
+			const bool same = ((c >> i) & 1u) == ((c >> j) & 1u);
+			m += same ? w * t[c] : -(w * t[c]);
+		}
+		r[j] = __builtin_fmaf(u[i], m, r[j]);
+		r[i] = __builtin_fmaf(u[j], m, r[i]);
+	}
+	const float s2 = s.scale * s.scale;
+#pragma unroll
+	for (int d = 0; d < 3; ++d) r[d] *= s2;
+}
+
 } // namespace neus

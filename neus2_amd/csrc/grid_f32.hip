@@ -162,6 +162,28 @@ __global__ void __launch_bounds__(256) k_grid_f32_bbi(uint32_t n, const GridLeve
 	}
 }
 
+// dL_dinput of backward_backward_input with a float table (k_grid_ddx of grid.hip with T = float and the caller's
+// dL_doutput layout): per (level, sample) terms into partial [3 l + d][n], summed in level order by k_grid_ddx_sum
+__global__ void __launch_bounds__(256) k_grid_f32_ddx(uint32_t n, const GridLevels gl, const float* __restrict__ coords, const float* __restrict__ table,
+                                                      const float* __restrict__ dLdy, uint32_t layout, const float* __restrict__ ddx,
+                                                      float* __restrict__ partial) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y, L = gl.n_levels;
+	if (i >= n) return;
+	const LevelSetup s = level_setup(gl, l, coords[(size_t)i * 3], coords[(size_t)i * 3 + 1], coords[(size_t)i * 3 + 2]);
+	float v[8][2];
+	uint32_t e[8];
+	gather_f32(s, table + (size_t)gl.offset[l] * 2, v, e);
+	const float g0 = dLdy[enc_addr(layout, n, L, i, 2 * l)], g1 = dLdy[enc_addr(layout, n, L, i, 2 * l + 1)];
+	float t[8];
+#pragma unroll
+	for (int k = 0; k < 8; ++k) t[k] = __builtin_fmaf(v[k][0], g0, v[k][1] * g1);
+	const float u[3] = {ddx[(size_t)i * 3], ddx[(size_t)i * 3 + 1], ddx[(size_t)i * 3 + 2]};
+	float r[3];
+	level_ddx(s, t, u, r);
+#pragma unroll
+	for (int d = 0; d < 3; ++d) partial[(size_t)(3 * l + d) * n + i] = r[d];
+}
+
 void check_layout(uint32_t layout) {
 	if (layout != ENC_LAYOUT_AOS && layout != ENC_LAYOUT_SOA) throw std::runtime_error("fp32 HashGrid: output layout AoS or SoA");
 }
@@ -185,6 +207,15 @@ void launch_grid_f32_bbi(hipStream_t s, uint32_t n, const GridLevels& gl, uint32
                          const float* dLdy, uint32_t layout, float* grads, const float* dydx, float* ddLdy) {
 	check_layout(layout);
 	if (n) k_grid_f32_bbi<<<dim3((n + 255) / 256, gl.n_levels), 256, 0, s>>>(n, gl, valid_level, coords, ddx, dLdy, layout, grads, dydx, ddLdy);
+}
+
+void launch_grid_f32_ddx(hipStream_t s, uint32_t n, const GridLevels& gl, uint32_t valid_level, const float* coords, const float* table,
+                         const float* dLdy, uint32_t layout, const float* ddx, float* partial, float* dLdx) {
+	check_layout(layout);
+	if (!n) return;
+	const uint32_t na = grid_ddx_active_levels(gl, valid_level);
+	if (na) k_grid_f32_ddx<<<dim3((n + 255) / 256, na), 256, 0, s>>>(n, gl, coords, table, dLdy, layout, ddx, partial);
+	launch_grid_ddx_sum(s, n, na, partial, dLdx);
 }
 
 }  // namespace neus

@@ -470,6 +470,15 @@ void launch_grid_f32_backward(hipStream_t s, uint32_t n, const GridLevels& gl, u
                               uint32_t layout, float* grads, const float* dydx, float* dLdx);
 void launch_grid_f32_bbi(hipStream_t s, uint32_t n, const GridLevels& gl, uint32_t valid_level, const float* coords, const float* ddx,
                          const float* dLdy, uint32_t layout, float* grads, const float* dydx, float* ddLdy);
+// dL_dinput of backward_backward_input (grid.h:1010-1181): d/dx of dL_ddLdinput . dL/dx, [n][3] f32, overwritten. g = dL_dy
+// (fp16: paired [L][ld] half2; fp32: the caller's layout), partial = scratch of 3 n_levels n floats; the levels of a
+// sample are summed in level order (bitwise repeatable, no atomics); levels past valid_level contribute 0
+uint32_t grid_ddx_active_levels(const GridLevels& gl, uint32_t valid_level);
+void launch_grid_ddx_sum(hipStream_t s, uint32_t n, uint32_t n_active, const float* partial, float* dLdx);
+void launch_grid_ddx(hipStream_t s, uint32_t n, uint32_t ld, const float* coords, const GridLevels& gl, uint32_t valid_level, const half_t* grid,
+                     const half_t* g, const float* ddx, float* partial, float* dLdx);
+void launch_grid_f32_ddx(hipStream_t s, uint32_t n, const GridLevels& gl, uint32_t valid_level, const float* coords, const float* table,
+                         const float* dLdy, uint32_t layout, const float* ddx, float* partial, float* dLdx);
 // paired [L][n] <-> sample rows [n][ld] (features in columns [0, 2L), zero padding up to ld): a FullyFusedMLP's input
 void launch_enc_to_rows(hipStream_t s, uint32_t n, uint32_t L, const uint32_t* paired, half_t* rows, uint32_t ld);
 void launch_enc_from_rows(hipStream_t s, uint32_t n, uint32_t L, const half_t* rows, uint32_t ld, uint32_t* paired);

@@ -1626,6 +1626,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
 				H1pB[2 * mt] = mask_frag(acc, 0, H0B[2 * mt]);
 				if (2 * mt + 1 < HKS) H1pB[2 * mt + 1] = mask_frag(acc, 1, H0B[2 * mt + 1]);
 			}
+			if (a.out) {  // dL_ddLdoutput = W1 h1' (the front carried through the output matrix; the forward's last layer on h1')
+				f16v acc = zero16();
+#pragma unroll
+				for (int ks = 0; ks < HKS; ++ks) acc = mfma(loadA(w1, 16, r, 16 * ks, h), H1pB[ks], acc);
+				if (valid)
+#pragma unroll
+					for (int reg = 0; reg < 8; ++reg) a.out[(size_t)i * 16 + acc_row(reg, h)] = (half_t)acc[reg];
+			}
 			// dW0 += b2 u^T, dW1 += dL h1'^T
 #pragma unroll
 			for (int kt = 0; kt < DMT; ++kt) {

@@ -3288,6 +3288,7 @@ struct NeusModule {
 	bool f32 = false;                   // Encoding created with requested_precision fp32: float params / output / gradients
 	Dev<uint32_t> enc_tmp, denc_tmp;    // paired-layout staging of non-paired module I/O
 	Dev<float> gtmp;                    // gradients of an Accumulate call (and of every fp16-gradient call)
+	Dev<float> ddx_partial;             // backward_backward_input's dL_dinput: per-level terms [3 L][capacity] (first use)
 	Dev<float4> dpos, v4;
 	Dev<half_t> zero_h;
 	Dev<float4> zero_v;
@@ -3324,6 +3325,16 @@ struct NeusModule {
 	void finish_grad(void* dL_dparams, int mode, hipStream_t s) {
 		if (grad_fp16) launch_grad_to_half(s, (uint32_t)n_params(), gtmp.p, (half_t*)dL_dparams, mode == NEUS_GRADIENT_ACCUMULATE);
 		else if (mode == NEUS_GRADIENT_ACCUMULATE) launch_add_f32(s, (uint32_t)n_params(), gtmp.p, (float*)dL_dparams);
+	}
+	float* ddx_scratch() { ddx_partial.alloc((size_t)3 * core.lay.L * capacity); return ddx_partial.p; }
+	// backward_backward_input's dL_ddLdoutput / dL_dinput of a network: the fronts / backs chain has no act'' term, so they
+	// are exact only where act'' = 0 (hidden ReLU or None) and the output is linear
+	void check_bbi_exact(const void* dL_ddLdoutput, const float* dL_dinput) const {
+		if (!dL_ddLdoutput && !dL_dinput) return;
+		if (kind == DensityNet || ((ff.act == FF_RELU || ff.act == FF_NONE) && ff.out_act == FF_NONE)) return;
+		throw std::runtime_error("backward_backward_input: dL_ddLdoutput and dL_dinput are exact only for hidden activation ReLU or None with "
+		                         "output activation None (the second derivative of any other activation is not implemented); pass null "
+		                         "for both to get the parameter gradients alone");
 	}
 	// a caller-layout encoding tensor (dL_doutput) as the kernels' paired layout
 	const half_t* paired_in(const void* x, uint32_t n, hipStream_t s) {
@@ -3623,10 +3634,12 @@ const half_t* ff_backward_chain(NeusModule* m, hipStream_t s, uint32_t n, const 
 	}
 	return d;
 }
-// FullyFusedMLP::backward_backward_input_impl (fully_fused_mlp.cu:1088-1198), parameter gradients only, with the front
-// f_0 = the network's dL_ddLdinput already in m->ff_front as rows [n][in_pad]: fronts f_i = act'(h_{i-1}) (W_{i-1} f_{i-1});
-// backs b_{N+2} = dL_doutput, b_i = act'(h_{i-2}) (W_{i-1}^T b_{i+1}); dW_{i-1} = b_{i+1} f_{i-1}^T into the partials
-void ff_bbi_chain(NeusModule* m, hipStream_t s, uint32_t n, const void* params, const half_t* acts, const half_t* dL_doutput) {
+// FullyFusedMLP::backward_backward_input_impl (fully_fused_mlp.cu:1088-1198) with the front f_0 = the network's
+// dL_ddLdinput already in m->ff_front as rows [n][in_pad]: fronts f_i = act'(h_{i-1}) (W_{i-1} f_{i-1}); dL_ddLdoutput (when
+// asked for) = the front carried through the output matrix, f_{N+1} = W_N f_N, as [n][out_pad] fp16; with wgrad the backs
+// b_{N+2} = dL_doutput, b_i = act'(h_{i-2}) (W_{i-1}^T b_{i+1}) and dW_{i-1} = b_{i+1} f_{i-1}^T into the partials
+void ff_bbi_chain(NeusModule* m, hipStream_t s, uint32_t n, const void* params, const half_t* acts, const half_t* dL_doutput, bool wgrad,
+                  half_t* dL_ddLdoutput) {
 	const FfNet& f = m->ff;
 	half_t* fr = m->ff_front.p;
 	auto front = [&](uint32_t i) { return i == 0 ? fr : fr + (size_t)n * f.in_pad + (size_t)(i - 1) * n * f.W; };
@@ -3636,6 +3649,12 @@ void ff_bbi_chain(NeusModule* m, hipStream_t s, uint32_t n, const void* params, 
 		L.aux = ff_hidden(f, const_cast<half_t*>(acts), n, i - 1); L.ldx = f.W;
 		launch_ff_layer(s, L);
 	}
+	if (dL_ddLdoutput) {
+		FfLayer L = ff_layer(ff_mat(f, params, f.N), f.rows[f.N], f.cols[f.N], false, front(f.N), f.W, n);
+		L.mode = FF_MODE_ACT; L.act = FF_NONE; L.out = dL_ddLdoutput; L.ldo = f.out_pad;
+		launch_ff_layer(s, L);
+	}
+	if (!wgrad) return;
 	const half_t* b = dL_doutput;
 	uint32_t ldb = f.out_pad;
 	int pp = 0;
@@ -3966,37 +3985,25 @@ int neus_module_backward_backward_input(NeusModule* m, void* stream, const NeusC
 			// (x scale; the padded rows, which the reference leaves uninitialised, are 0: the constant padding has no input
 			// gradient); FullyFusedMLP::backward_backward_input_impl (fully_fused_mlp.cu:1088-1198): fronts f_0 = u,
 			// f_i = act'(h_{i-1}) (W_{i-1} f_{i-1}); backs b_{N+2} = dL_doutput, b_i = act'(h_{i-2}) (W_{i-1}^T b_{i+1});
-			// dW_{i-1} = b_{i+1} f_{i-1}^T. Like the reference, dL_ddLdoutput and dL_dinput are not produced.
+			// dW_{i-1} = b_{i+1} f_{i-1}^T. dL_ddLdoutput = W_N f_N (the front carried through the output matrix); dL_dinput = 0:
+			// with act'' = 0 the first derivative is piecewise constant in the input.
 			if (!ctx || ctx->n != n || !ctx->acts.p) throw std::runtime_error("backward_backward_input: needs the forward's context");
 			if (!dL_ddLdinput || !dL_doutput || !params) throw std::runtime_error("backward_backward_input: null input");
 			m->check_n(n, true);
+			m->check_bbi_exact(dL_ddLdoutput, dL_dinput);
 			HIP_CHECK(hipSetDevice(m->core.device));
 			StreamSwap sw(m->core, stream);
 			hipStream_t s = m->core.stream;
 			float* g = m->grad_target(dL_dparams, gradient_mode);
-			if (!g) return;
+			if (dL_dinput) HIP_CHECK(hipMemsetAsync(dL_dinput, 0, (size_t)n * m->ff.n_in * 4, s));
+			if (!g && !dL_ddLdoutput) return;
 			const FfNet& f = m->ff;
-			half_t* fr = m->ff_front.p;
-			auto front = [&](uint32_t i) { return i == 0 ? fr : fr + (size_t)n * f.in_pad + (size_t)(i - 1) * n * f.W; };
-			launch_ff_input(s, n, f.n_in, f.in_pad, dL_ddLdinput, f.in_scale, 0.f, fr, true);
-			for (uint32_t i = 1; i <= f.N; ++i) {
-				FfLayer L = ff_layer(ff_mat(f, params, i - 1), f.rows[i - 1], f.cols[i - 1], false, front(i - 1), i == 1 ? f.in_pad : f.W, n);
-				L.mode = FF_MODE_DACT; L.act = f.act; L.out = front(i); L.ldo = f.W;
-				L.aux = ff_hidden(f, ctx->acts.p, n, i - 1); L.ldx = f.W;
-				launch_ff_layer(s, L);
+			launch_ff_input(s, n, f.n_in, f.in_pad, dL_ddLdinput, f.in_scale, 0.f, m->ff_front.p, true);
+			ff_bbi_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, g != nullptr, (half_t*)dL_ddLdoutput);
+			if (g) {
+				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
+				m->finish_grad(dL_dparams, gradient_mode, s);
 			}
-			const half_t* b = (const half_t*)dL_doutput;
-			uint32_t ldb = f.out_pad;
-			int pp = 0;
-			for (uint32_t l = f.N + 1; l-- > 0;) {  // dW_l = b_{l+2} f_l^T, then b_{l+1} through W_l
-				ff_wgrad(f, s, n, l, b, ldb, front(l), l == 0 ? f.in_pad : f.W, m->ff_partial.p);
-				if (l > 0) {
-					ff_back_through(f, s, n, params, l, b, ldb, ctx->acts.p, m->ff_d[pp].p);
-					b = m->ff_d[pp].p; pp ^= 1; ldb = f.W;
-				}
-			}
-			launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
-			m->finish_grad(dL_dparams, gradient_mode, s);
 			HIP_CHECK(hipGetLastError());
 			return;
 		}
@@ -4005,26 +4012,38 @@ int neus_module_backward_backward_input(NeusModule* m, void* stream, const NeusC
 			// backward gives dL/d(encoding) (parameter gradients ignored); (2) the HashGrid's backward_backward_input with it as
 			// dL_doutput: the second-order grid gradient and pos_encoding_dy = dy/dx . dL_ddLdinput (grid.h:1697-1800); (3) the
 			// FullyFusedMLP's backward_backward_input with pos_encoding_dy as its dL_ddLdinput (fully_fused_mlp.cu:1088-1198).
-			// Like the reference, dL_ddLdoutput and dL_dinput are not produced.
+			// dL_ddLdoutput = the front through the output matrix (J_mlp J_enc dL_ddLdinput); dL_dinput = the HashGrid's second
+			// derivative in x (k_grid_ddx) with dL/d(encoding) as its dL_doutput.
 			if (!ctx || ctx->n != n || !ctx->dydx.p || !ctx->acts.p) throw std::runtime_error("backward_backward_input: needs the forward's context");
 			if (!input || !dL_ddLdinput || !dL_doutput || !params) throw std::runtime_error("backward_backward_input: null input");
 			m->check_n(n, true);
+			m->check_bbi_exact(dL_ddLdoutput, dL_dinput);
 			HIP_CHECK(hipSetDevice(m->core.device));
 			StreamSwap sw(m->core, stream);
 			NeusTestbed& t = m->core;
 			hipStream_t s = t.stream;
 			float* g = m->grad_target(dL_dparams, gradient_mode);
-			if (!g) return;
+			if (!g && !dL_ddLdoutput && !dL_dinput) return;
 			const FfNet& f = m->ff;
-			const half_t* dX0 = ff_backward_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, nullptr, false);
-			launch_enc_from_rows(s, n, t.lay.L, dX0, f.in_pad, m->denc_tmp.p);
-			launch_enc_ddLdoutput(s, n, n, t.lay.L, dL_ddLdinput, ctx->dydx.p, (half_t*)m->u_tmp.p, m->v4.p);
-			launch_grid_scatter(s, nullptr, n, n, input, 3, t.gl, m->valid(), m->zero_h.p, (const half_t*)m->denc_tmp.p, m->v4.p, g + f.P,
-			                    t.swork, t.scan_tmp.p, t.scan_tmp_bytes);
-			launch_enc_to_rows(s, n, t.lay.L, m->u_tmp.p, m->ff_front.p, f.in_pad);
-			ff_bbi_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput);
-			launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
-			m->finish_grad(dL_dparams, gradient_mode, s);
+			if (g || dL_dinput) {
+				const half_t* dX0 = ff_backward_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, nullptr, false);
+				launch_enc_from_rows(s, n, t.lay.L, dX0, f.in_pad, m->denc_tmp.p);
+			}
+			if (g || dL_ddLdoutput) launch_enc_ddLdoutput(s, n, n, t.lay.L, dL_ddLdinput, ctx->dydx.p, (half_t*)m->u_tmp.p, m->v4.p);
+			if (g)
+				launch_grid_scatter(s, nullptr, n, n, input, 3, t.gl, m->valid(), m->zero_h.p, (const half_t*)m->denc_tmp.p, m->v4.p, g + f.P,
+				                    t.swork, t.scan_tmp.p, t.scan_tmp_bytes);
+			if (dL_dinput)
+				launch_grid_ddx(s, n, n, input, t.gl, m->valid(), (const half_t*)params + f.P, (const half_t*)m->denc_tmp.p, dL_ddLdinput,
+				                m->ddx_scratch(), dL_dinput);
+			if (g || dL_ddLdoutput) {
+				launch_enc_to_rows(s, n, t.lay.L, m->u_tmp.p, m->ff_front.p, f.in_pad);
+				ff_bbi_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, g != nullptr, (half_t*)dL_ddLdoutput);
+			}
+			if (g) {
+				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
+				m->finish_grad(dL_dparams, gradient_mode, s);
+			}
 			HIP_CHECK(hipGetLastError());
 			return;
 		}
@@ -4032,7 +4051,8 @@ int neus_module_backward_backward_input(NeusModule* m, void* stream, const NeusC
 			// NetworkWithInputEncoding::backward_backward_input (network_with_input_encoding.h:159-250): u = dy/dx . dL_ddLdinput
 			// (kernel_grid_backward_input_backward_dLdoutput), the MLP's backward-backward (fully_fused_mlp.cu:1088-1198: b2 =
 			// relu'(H0) W1^T dL, h1' = relu'(H0) W0 u; dW0 = b2 u^T, dW1 = dL h1'^T) and the encoding's second-order grid
-			// gradient with dL/d(encoding) = W0^T b2. Like the reference, dL_ddLdoutput and dL_dinput are not produced.
+			// gradient with dL/d(encoding) = W0^T b2. dL_ddLdoutput = W1 h1' (one more MFMA of the fused kernel); dL_dinput = the
+			// HashGrid's second derivative in x (k_grid_ddx) with dL/d(encoding) as its dL_doutput.
 			if (!ctx || ctx->n != n || !ctx->dydx.p || !ctx->enc.p) throw std::runtime_error("backward_backward_input: needs the forward's context");
 			if (!input || !dL_ddLdinput || !dL_doutput || !params) throw std::runtime_error("backward_backward_input: null input");
 			m->check_n(n, true);
@@ -4041,21 +4061,25 @@ int neus_module_backward_backward_input(NeusModule* m, void* stream, const NeusC
 			NeusTestbed& t = m->core;
 			hipStream_t s = t.stream;
 			float* g = m->grad_target(dL_dparams, gradient_mode);
-			if (!g) return;
+			if (!g && !dL_ddLdoutput && !dL_dinput) return;
 			const half_t* ph = (const half_t*)params;
 			launch_enc_ddLdoutput(s, n, n, t.lay.L, dL_ddLdinput, ctx->dydx.p, (half_t*)m->u_tmp.p, m->v4.p);
 			DNetLaunch d{};
 			d.w0 = ph; d.w1 = ph + (size_t)m->dn_width * m->dn_de; d.enc = ctx->enc.p; d.dL = (const half_t*)dL_doutput; d.u = m->u_tmp.p;
-			d.denc = m->denc_tmp.p; d.wpartial = m->dn_partial.p;
+			d.denc = m->denc_tmp.p; d.wpartial = m->dn_partial.p; d.out = (half_t*)dL_ddLdoutput;
 			launch_dnet(s, t.lay.L, m->dn_width, 2, n, d);
-			launch_mlp_grad_reduce(s, MlpGradReduce{m->dn_partial.p, dnet_blocks(n), m->n_mlp, g, nullptr, nullptr, 0, m->dn_dummy.p});
-			launch_grid_scatter(s, nullptr, n, n, input, 3, t.gl, m->valid(), m->zero_h.p, (const half_t*)m->denc_tmp.p, m->v4.p, g + m->n_mlp,
-			                    t.swork, t.scan_tmp.p, t.scan_tmp_bytes);
-			m->finish_grad(dL_dparams, gradient_mode, s);
+			if (g) {
+				launch_mlp_grad_reduce(s, MlpGradReduce{m->dn_partial.p, dnet_blocks(n), m->n_mlp, g, nullptr, nullptr, 0, m->dn_dummy.p});
+				launch_grid_scatter(s, nullptr, n, n, input, 3, t.gl, m->valid(), m->zero_h.p, (const half_t*)m->denc_tmp.p, m->v4.p, g + m->n_mlp,
+				                    t.swork, t.scan_tmp.p, t.scan_tmp_bytes);
+			}
+			if (dL_dinput)
+				launch_grid_ddx(s, n, n, input, t.gl, m->valid(), ph + m->n_mlp, (const half_t*)m->denc_tmp.p, dL_ddLdinput, m->ddx_scratch(),
+				                dL_dinput);
+			if (g) m->finish_grad(dL_dparams, gradient_mode, s);
 			HIP_CHECK(hipGetLastError());
 			return;
 		}
-		if (dL_dinput) throw std::runtime_error("HashGrid backward_backward_input: dL_dinput (second derivative in x) is not provided");
 		if (!ctx || ctx->n != n || !ctx->dydx.p) throw std::runtime_error("backward_backward_input: needs the forward's context (dy/dx)");
 		if (!input || !dL_ddLdinput || !dL_doutput) throw std::runtime_error("backward_backward_input: null input");
 		m->check_n(n, true);
@@ -4067,6 +4091,11 @@ int neus_module_backward_backward_input(NeusModule* m, void* stream, const NeusC
 		if (m->f32) {  // GridEncoding<float>::backward_backward_input (grid.h:880-1007 with GRAD_T = float)
 			if (g) HIP_CHECK(hipMemsetAsync(g, 0, (size_t)m->n_params() * 4, s));
 			launch_grid_f32_bbi(s, n, t.gl, m->valid(), input, dL_ddLdinput, (const float*)dL_doutput, m->layout, g, ctx->dydx.p, (float*)dL_ddLdoutput);
+			if (dL_dinput) {  // kernel_grid_backward_input_backward_input (grid.h:1010-1181)
+				if (!params) throw std::runtime_error("module: null params");
+				launch_grid_f32_ddx(s, n, t.gl, m->valid(), input, (const float*)params, (const float*)dL_doutput, m->layout, dL_ddLdinput,
+				                    m->ddx_scratch(), dL_dinput);
+			}
 			if (g) m->finish_grad(dL_dparams, gradient_mode, s);
 			HIP_CHECK(hipGetLastError());
 			return;
@@ -4075,14 +4104,17 @@ int neus_module_backward_backward_input(NeusModule* m, void* stream, const NeusC
 		const bool relay = m->layout != ENC_LAYOUT_PAIRED && dL_ddLdoutput;
 		launch_enc_ddLdoutput(s, n, n, t.lay.L, dL_ddLdinput, ctx->dydx.p, relay ? (half_t*)m->enc_tmp.p : (half_t*)dL_ddLdoutput, m->v4.p);
 		if (relay) launch_enc_to_layout(s, n, t.lay.L, m->enc_tmp.p, (half_t*)dL_ddLdoutput, m->layout);
-		if (g) {
+		if (g || dL_dinput) {
 			m->load_params(params, s);
 			const half_t* dly = m->paired_in(dL_doutput, n, s);
 			// kernel_grid_backward_input_backward_grid (grid.h:880-1007): the fused scatter's second-order term with
 			// g = dL_doutput, v = dL_ddLdinput, first-order term zero
-			launch_grid_scatter(s, nullptr, n, n, input, 3, t.gl, m->valid(), m->zero_h.p, dly, m->v4.p, g, t.swork,
-			                    t.scan_tmp.p, t.scan_tmp_bytes);
-			m->finish_grad(dL_dparams, gradient_mode, s);
+			if (g)
+				launch_grid_scatter(s, nullptr, n, n, input, 3, t.gl, m->valid(), m->zero_h.p, dly, m->v4.p, g, t.swork,
+				                    t.scan_tmp.p, t.scan_tmp_bytes);
+			if (dL_dinput)  // kernel_grid_backward_input_backward_input (grid.h:1010-1181)
+				launch_grid_ddx(s, n, n, input, t.gl, m->valid(), t.params_h.p + t.lay.grid_off, dly, dL_ddLdinput, m->ddx_scratch(), dL_dinput);
+			if (g) m->finish_grad(dL_dparams, gradient_mode, s);
 		}
 		HIP_CHECK(hipGetLastError());
 	});

@@ -189,11 +189,14 @@ class Module:
         return dL_dparams, dL_dinput
 
     def backward_backward_input(self, ctx, x, dL_ddLdinput, dL_doutput, params, dL_dparams=None, dL_ddLdoutput=None,
-                                mode=GradientMode.Overwrite):
+                                mode=GradientMode.Overwrite, dL_dinput=None):
+        """With S = dL_ddLdinput . dL/dx: dL_dparams = dS/dparams, dL_ddLdoutput = dS/d(dL_doutput) (the output's shape and
+        precision) and dL_dinput = dS/dx ([n, n_input_dims] f32), each written only when given. The last two are provided
+        for hidden activation ReLU / None with a linear output (an error otherwise)."""
         if self.kind == "network":
             raise NeusError("backward_backward_input: the NerfNetwork's second order is inside backward")
         check(lib().neus_module_backward_backward_input(self._h, _stream(), ctx._h, C.c_uint32(ctx.n), _p(dL_ddLdinput), _p(x),
-                                                        _p(dL_doutput), _p(dL_dparams), _p(dL_ddLdoutput), None, _p(params),
+                                                        _p(dL_doutput), _p(dL_dparams), _p(dL_ddLdoutput), _p(dL_dinput), _p(params),
                                                         C.c_int(int(mode))))
         return dL_dparams, dL_ddLdoutput
 
