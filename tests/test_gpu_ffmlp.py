@@ -6,7 +6,9 @@ float64 torch restatement on the same fp16 parameters:
 * backward: dL_dparams (fp32 precision mode) and dL_dinput vs autograd; Accumulate adds, fp16 mode rounds;
 * backward_backward_input (ReLU networks, linear output: tcnn's fronts / backs chain is exact there, relu'' = 0):
   dL_dparams vs the autograd gradient of <dL_ddLdinput, d<dL_doutput, y>/dx>.
-Tolerances: rel-L2 <= 2e-2 and cosine >= 0.999 per weight matrix (fp16 storage of activations and deltas)."""
+Tolerances: rel-L2 <= 2e-2 and cosine >= 0.999 per weight matrix (fp16 storage of activations and deltas).
+Every hidden activation the kernels implement is named (ReLU, Softplus, Sigmoid, Squareplus); the non-ReLU cases run a
+second time at n = 2176 (three k_ff_wgrad blocks), where the exact-integer test (test_gpu_ffmlp_exact.py) cannot go."""
 import os
 
 import numpy as np
@@ -21,7 +23,11 @@ CASES = [
     dict(n_in=40, n_out=4, W=128, N=3, act="ReLU", out_act="Sigmoid"),
     dict(n_in=20, n_out=1, W=32, N=2, act="Softplus", out_act="Exponential"),
     dict(n_in=8, n_out=5, W=64, N=1, act="Sigmoid", out_act="None"),
+    dict(n_in=12, n_out=2, W=32, N=2, act="Squareplus", out_act="None"),
 ]
+# every case at n = 512 (one k_ff_wgrad block); the Softplus / Exponential, Sigmoid and Squareplus ones also at n = 2176 of a
+# capacity of 4096: three weight-gradient blocks of 726 samples (a ragged last chunk, unaligned block starts)
+RUNS = list(range(len(CASES))) + [pytest.param((i, 2176), id=f"{i}-n2176") for i in (3, 4, 5)]
 
 
 def _record(test, **metrics):
@@ -40,6 +46,8 @@ def _act(name, x, torch):
         return torch.sigmoid(x)
     if name == "Softplus":
         return torch.log(torch.exp(x * 10.0) + 1.0) / 10.0
+    if name == "Squareplus":
+        return 0.5 * (x * 10.0 + torch.sqrt((x * 10.0) ** 2 + 4.0)) / 10.0
     return x
 
 
@@ -86,11 +94,11 @@ def _ref_forward(c, mats, x, torch):
     return h
 
 
-def _net(c, precision="fp32"):
+def _net(c, precision="fp32", capacity=1024):
     from neus2_amd.module import Module
     return Module.create_network(c["n_in"], c["n_out"], {"otype": "FullyFusedMLP", "n_neurons": c["W"], "n_hidden_layers": c["N"],
                                                           "activation": c["act"], "output_activation": c["out_act"],
-                                                          "gradient_precision": precision}, batch_capacity=1024)
+                                                          "gradient_precision": precision}, batch_capacity=capacity)
 
 
 def _rel_cos(x, y):
@@ -98,14 +106,17 @@ def _rel_cos(x, y):
     return np.linalg.norm(x - y) / max(np.linalg.norm(y), 1e-30), x @ y / max(np.linalg.norm(x) * np.linalg.norm(y), 1e-30)
 
 
-@pytest.mark.parametrize("case", range(len(CASES)))
+@pytest.mark.parametrize("case", RUNS)
 def test_ffmlp_module(torch_cuda, case):
     import oracle as O
     from neus2_amd.module import GradientMode
     t = torch_cuda
+    case, n = case if isinstance(case, tuple) else (case, 512)
+    capacity = 1024 if n == 512 else 4096
+    tag = str(case) if n == 512 else f"{case}_n{n}"
     c = CASES[case]
     shapes, in_pad, out_pad = _shapes(c)
-    m = _net(c)
+    m = _net(c, capacity=capacity)
     P = sum(r * k for r, k in shapes)
     assert m.n_params == P and m.n_input_dims == c["n_in"] and m.n_output_dims == out_pad
     assert m.hyperparams()["network"]["n_hidden_layers"] == c["N"]
@@ -122,7 +133,6 @@ def test_ffmlp_module(torch_cuda, case):
     # moderate weights so every activation stays in its interesting range
     p16 = (p32 * 0.8).astype(np.float16)
     params = t.from_numpy(p16.view(np.int16)).cuda()
-    n = 512
     rng = np.random.default_rng(case)
     x = rng.uniform(-1, 1, (n, c["n_in"])).astype(np.float32)
     xd = t.from_numpy(x).cuda()
@@ -134,7 +144,7 @@ def test_ffmlp_module(torch_cuda, case):
     yr = _ref_forward(c, mats, xr, t)
     err = np.abs(got - yr.detach().numpy())
     tol = 2e-2 * np.abs(yr.detach().numpy()) + 5e-3
-    _record(f"ffmlp_forward_{case}", frac_within=(err <= tol).mean(), max_err=err.max())
+    _record(f"ffmlp_forward_{tag}", frac_within=(err <= tol).mean(), max_err=err.max())
     assert (err <= tol).mean() >= 0.995, (err.max(), (err <= tol).mean())
     # backward: dL_dparams (fp32 mode) and dL_dinput vs autograd
     dL = rng.normal(0, 1, (n, out_pad)).astype(np.float16)
@@ -147,17 +157,17 @@ def test_ffmlp_module(torch_cuda, case):
     off = 0
     for l, (r, k) in enumerate(shapes):
         rel, cos = _rel_cos(g.cpu().numpy()[off: off + r * k], gref[off: off + r * k])
-        _record(f"ffmlp_backward_{case}_W{l}", rel=rel, cos=cos)
+        _record(f"ffmlp_backward_{tag}_W{l}", rel=rel, cos=cos)
         assert rel <= 2e-2 and cos >= 0.999, (l, rel, cos)
         off += r * k
     rel, cos = _rel_cos(dx.cpu().numpy(), xr.grad.numpy())
-    _record(f"ffmlp_dinput_{case}", rel=rel, cos=cos)
+    _record(f"ffmlp_dinput_{tag}", rel=rel, cos=cos)
     assert rel <= 2e-2 and cos >= 0.999, (rel, cos)
     # Accumulate adds to the caller's buffer; fp16 gradients are the fp32 ones rounded
     g2 = g.clone()
     m.backward(ctx, xd, dLd, params, dL_dparams=g2, mode=GradientMode.Accumulate, output=y)
     np.testing.assert_allclose(g2.cpu().numpy(), 2 * g.cpu().numpy(), rtol=1e-6, atol=1e-30)
-    m16 = _net(c, "fp16")
+    m16 = _net(c, "fp16", capacity)
     ctx16, y16 = m16.forward(xd, params)
     g16 = m16.gradient_buffer()
     m16.backward(ctx16, xd, dLd, params, dL_dparams=g16, output=y16)

@@ -22,6 +22,9 @@ CASES = [
     dict(L=6, W=64, NH=1, act="ReLU", out_act="Sigmoid", n_out=3),
     dict(L=4, W=128, NH=3, act="ReLU", out_act="None", n_out=16),
 ]
+# every case at N = 1024 (one k_ff_wgrad block); case 0 also at n = 2176 of a capacity of 4096: three weight-gradient blocks
+# of 726 samples (a ragged last chunk, unaligned block starts) behind the grid kernels
+RUNS = list(range(len(CASES))) + [pytest.param((0, 2176, 4096), id="0-n2176")]
 
 
 def _record(test, **metrics):
@@ -52,12 +55,14 @@ def _act(name, x, torch):
     return {"ReLU": torch.relu, "Sigmoid": torch.sigmoid}.get(name, lambda v: v)(x)
 
 
-@pytest.mark.parametrize("case", range(len(CASES)))
+@pytest.mark.parametrize("case", RUNS)
 def test_grid_mlp_module(torch_cuda, case):
     import torch
     from torch_ref import grid_tables, hash_grid
     from neus2_amd.module import GradientMode, Module
     t = torch_cuda
+    case, n, capacity = case if isinstance(case, tuple) else (case, N, N)
+    tag = str(case) if n == N else f"{case}_n{n}"
     c = CASES[case]
     L, W, NH = c["L"], c["W"], c["NH"]
     log2t = 14
@@ -65,7 +70,7 @@ def test_grid_mlp_module(torch_cuda, case):
                "per_level_scale": 1.5}
     net_cfg = {"otype": "FullyFusedMLP", "activation": c["act"], "output_activation": c["out_act"], "n_neurons": W,
                "n_hidden_layers": NH, "gradient_precision": "fp32"}
-    m = Module.create_network_with_input_encoding(3, c["n_out"], enc_cfg, net_cfg, batch_capacity=N)
+    m = Module.create_network_with_input_encoding(3, c["n_out"], enc_cfg, net_cfg, batch_capacity=capacity)
     DE = (2 * L + 15) // 16 * 16
     out_pad = (c["n_out"] + 15) // 16 * 16
     shapes = [(W, DE)] + [(W, W)] * (NH - 1) + [(out_pad, W)]
@@ -85,7 +90,7 @@ def test_grid_mlp_module(torch_cuda, case):
     mats_h = [rng.normal(0, 1.2 / np.sqrt(k), (r, k)) for r, k in shapes]
     ph = np.concatenate([a.ravel() for a in mats_h] + [rng.uniform(-1, 1, 2 * off[-1])]).astype(np.float16)
     params = t.from_numpy(ph.view(np.int16).copy()).cuda()
-    pos = rng.uniform(0.02, 0.98, (N, 3)).astype(np.float32)
+    pos = rng.uniform(0.02, 0.98, (n, 3)).astype(np.float32)
     x = t.from_numpy(pos).cuda()
     ctx, y = m.forward(x, params, prepare_input_gradients=True)
     r16 = _r16_fn(torch)
@@ -116,15 +121,17 @@ def test_grid_mlp_module(torch_cuda, case):
     yo, ro = y.float().cpu().numpy(), out.detach().numpy()
     err = np.abs(yo - ro)
     within = np.mean(err <= 1e-2 * np.abs(ro) + 4e-3)
-    _record(f"grid_mlp_forward_{case}", frac_within=within, max_err=err.max())
+    _record(f"grid_mlp_forward_{tag}", frac_within=within, max_err=err.max())
     assert within >= 0.99, err.max()
     # both sides round the same fp16 inputs; a hidden pre-activation whose fp32 sum sits within the accumulation-order
     # error of 0 may take the other ReLU branch on the device: dL = 0 for those samples
-    ambiguous = np.zeros(N, bool)
+    ambiguous = np.zeros(n, bool)
     for z in pre[:-1]:
         ambiguous |= (np.abs(z.detach().numpy()) < 1e-4).any(axis=1)
     assert ambiguous.mean() < 0.3
-    dlo = rng.normal(0, 1, (N, out_pad)).astype(np.float16)
+    if n != N:
+        assert ambiguous.mean() <= 0.05
+    dlo = rng.normal(0, 1, (n, out_pad)).astype(np.float16)
     dlo[ambiguous] = 0
     dlo_t = torch.tensor(dlo.astype(np.float64))
     S = (out * dlo_t).sum()
@@ -132,7 +139,7 @@ def test_grid_mlp_module(torch_cuda, case):
     gmats, gtab, gx = grads[:len(mats)], grads[-2], grads[-1]
     dlo_dev = t.from_numpy(dlo.view(np.int16).copy()).cuda()
     g = t.zeros(m.n_params, dtype=t.float32, device="cuda")
-    dx = t.zeros((N, 3), dtype=t.float32, device="cuda")
+    dx = t.zeros((n, 3), dtype=t.float32, device="cuda")
     m.backward(ctx, x, dlo_dev, params, dL_dparams=g, dL_dinput=dx, mode=GradientMode.Overwrite, output=y)
     gm = g.cpu().numpy()
     blocks, o = {}, 0
@@ -142,7 +149,7 @@ def test_grid_mlp_module(torch_cuda, case):
     blocks["grid"] = (gm[n_mlp:], gtab)
     blocks["dinput"] = (dx.cpu().numpy(), gx)
     if c["out_act"] == "None":
-        v = rng.normal(0, 1, (N, 3)).astype(np.float32)
+        v = rng.normal(0, 1, (n, 3)).astype(np.float32)
         S2 = (gx * torch.tensor(v.astype(np.float64))).sum()
         g2 = torch.autograd.grad(S2, mats + [tab], allow_unused=True)
         gd2 = t.zeros(m.n_params, dtype=t.float32, device="cuda")
@@ -154,7 +161,7 @@ def test_grid_mlp_module(torch_cuda, case):
             o += r * k
         blocks["grid_2nd"] = (g2m[n_mlp:], g2[-1])
     res_ = {name: _rel_cos(a, b.detach().numpy()) for name, (a, b) in blocks.items()}
-    _record(f"grid_mlp_{case}", **{f"rel_{k}": v_[0] for k, v_ in res_.items()}, **{f"cos_{k}": v_[1] for k, v_ in res_.items()})
+    _record(f"grid_mlp_{tag}", **{f"rel_{k}": v_[0] for k, v_ in res_.items()}, **{f"cos_{k}": v_[1] for k, v_ in res_.items()})
     for name, (rel, cos) in res_.items():
         assert rel <= 2e-3 and cos >= 0.99999, (name, rel, cos)
 
