@@ -475,7 +475,17 @@ int neus_debug_host_group_allreduce(NeusHostGroup* group, void* host, uint64_t n
  *                                (cpp_api.h:110, cpp_api.cu:174-180): NEUS_PRECISION_FP16 = GridEncoding<__half> (the
  *                                kernels of the training step), NEUS_PRECISION_FP32 = GridEncoding<float>: params, output,
  *                                dL_doutput, dL_ddLdoutput and dL_dparams f32 (AoS / SoA layouts).
- *   neus_module_create_network_with_input_encoding  {HashGrid, Identity} -> FullyFusedMLP of any depth (below).
+ *                                Or a parameter-free encoding (encodings.hip) on any n_input_dims and any n >= 1:
+ *                                {"otype": "Identity", "scale", "offset"}, {"otype": "Frequency", "n_frequencies": 1..16}
+ *                                (output 2 D F), {"otype": "SphericalHarmonics", "degree": 1..8} (3 dims, output degree^2)
+ *                                or {"otype": "Composite", "nested": [{"n_dims_to_encode": k, ...}, ...]} of these three
+ *                                over consecutive input dims (<= 8; the last may omit n_dims_to_encode). n_params 0: params
+ *                                and dL_dparams may be NULL. Output / dL_doutput [n][w] ("AoS") or [w][n] ("SoA"), unpadded,
+ *                                fp16 or f32 by requested_precision. backward_backward_input: dL_ddLdoutput = J dL_ddLdinput
+ *                                for every type, dL_dinput for Identity and Frequency; with a SphericalHarmonics segment a
+ *                                non-NULL dL_dinput is an error ("not supported").
+ *   neus_module_create_network_with_input_encoding  {HashGrid, Identity, Frequency, SphericalHarmonics, Composite} ->
+ *                                FullyFusedMLP of any depth (below).
  *   neus_module_create_nerf_network  the NeuS NerfNetwork (nerf_network.h; the full config object with "encoding",
  *                                "network", "rgb_network"): input NerfCoordinate [n][7] f32 (pos, dt, dir), output
  *                                [n][16] fp16; params [n_params] fp16 in the layout of neus_testbed_layout. Its backward
@@ -517,7 +527,10 @@ int neus_module_create_encoding(uint32_t n_input_dims, const char* encoding_json
  * dims runs as one fused kernel; other shapes as the grid kernels feeding the FullyFusedMLP layers. backward_backward_input
  * follows network_with_input_encoding.h:159-250 / fully_fused_mlp.cu:1088-1198: parameter gradients, dL_ddLdoutput = J_mlp J_enc
  * dL_ddLdinput as [n][padded n_output_dims] fp16 and dL_dinput = the HashGrid's second derivative in x of dL/d(encoding) (see
- * above for the activations these two are provided for). */
+ * above for the activations these two are provided for). A Frequency, SphericalHarmonics or Composite encoding (as
+ * create_encoding's; encoded width <= 128) is written straight into the MLP's fp16 input rows, padded to 16 with ones; params
+ * are the network matrices alone; dL_dinput of backward_backward_input is the encoding's second-derivative term of dL/d(its
+ * output) (an error with a SphericalHarmonics segment). */
 int neus_module_create_network_with_input_encoding(uint32_t n_input_dims, uint32_t n_output_dims, const char* encoding_json,
                                                    const char* network_json, uint32_t batch_capacity, NeusModule** out);
 int neus_module_destroy(NeusModule* m);

@@ -3268,8 +3268,11 @@ struct NeusModule {
 	// implements (network_with_input_encoding.h:159-250, fully_fused_mlp.cu:1088-1198)
 	// Mlp: tcnn::cpp::create_network = NetworkWithInputEncoding(Identity -> FullyFusedMLP) (cpp_api.cu:170-172), ffmlp.hip
 	// GridMlp: NetworkWithInputEncoding(HashGrid -> any FullyFusedMLP), composed of the encoding kernels and ffmlp.hip's layers
-	enum Kind { Network = 0, Encoding = 1, DensityNet = 2, Mlp = 3, GridMlp = 4 } kind;
+	// PfEncoding: a parameter-free encoding (Identity, Frequency, SphericalHarmonics or a Composite of them), encodings.hip
+	// EncMlp: NetworkWithInputEncoding(such an encoding -> any FullyFusedMLP): encodings.hip writes the MLP's input rows
+	enum Kind { Network = 0, Encoding = 1, DensityNet = 2, Mlp = 3, GridMlp = 4, PfEncoding = 5, EncMlp = 6 } kind;
 	FfNet ff;
+	PfEnc pf{};                              // PfEncoding, EncMlp: the segments
 	Dev<half_t> ff_acts, ff_front, ff_d[2];  // Mlp: inference activations, backward-backward fronts, delta ping-pong
 	Dev<float> ff_partial, ff_dummy;         // Mlp: per-block weight-gradient rows
 	uint32_t n_mlp = 0, dn_width = 0, dn_de = 0;  // DensityNet: MLP parameters W DE + 16 W ahead of the grid, width, padded input
@@ -3294,7 +3297,8 @@ struct NeusModule {
 	Dev<float4> zero_v;
 	explicit NeusModule(int device) : core(device) {}
 	uint64_t n_params() const {
-		if (kind == Mlp) return ff.P;
+		if (kind == Mlp || kind == EncMlp) return ff.P;
+		if (kind == PfEncoding) return 0;
 		if (kind == GridMlp) return ff.P + core.lay.n_grid;
 		return kind == Network ? core.lay.P : (kind == DensityNet ? n_mlp + core.lay.n_grid : core.lay.n_grid);
 	}
@@ -3312,7 +3316,7 @@ struct NeusModule {
 		if (n > capacity) throw std::runtime_error("module: n_elements exceeds the module's batch capacity");
 		if (backward && kind == Network && (n == 0 || n % 128 != 0))
 			throw std::runtime_error("module backward: n_elements must be a positive multiple of 128 (fully_fused_mlp.cu:779-781)");
-		if ((kind == Mlp || kind == GridMlp) && n % 128 != 0) throw std::runtime_error("FullyFusedMLP: batch size must be a multiple of 128 (fully_fused_mlp.cu:779-781)");
+		if ((kind == Mlp || kind == GridMlp || kind == EncMlp) && n % 128 != 0) throw std::runtime_error("FullyFusedMLP: batch size must be a multiple of 128 (fully_fused_mlp.cu:779-781)");
 	}
 	// the destination of this call's parameter gradients (Overwrite: dL_dparams itself; Accumulate: a scratch buffer)
 	float* grad_target(void* dL_dparams, int mode) {
@@ -3325,6 +3329,21 @@ struct NeusModule {
 	void finish_grad(void* dL_dparams, int mode, hipStream_t s) {
 		if (grad_fp16) launch_grad_to_half(s, (uint32_t)n_params(), gtmp.p, (half_t*)dL_dparams, mode == NEUS_GRADIENT_ACCUMULATE);
 		else if (mode == NEUS_GRADIENT_ACCUMULATE) launch_add_f32(s, (uint32_t)n_params(), gtmp.p, (float*)dL_dparams);
+	}
+	bool pf_has_sh() const {
+		for (uint32_t q = 0; q < pf.n_seg; ++q) if (pf.seg[q].type == PF_SH) return true;
+		return false;
+	}
+	// a caller tensor of the stand-alone parameter-free encoding (output, dL_doutput, dL_ddLdoutput): unpadded AoS / SoA
+	PfView pf_view(const void* p, uint32_t n) const {
+		return layout == ENC_LAYOUT_SOA ? PfView{const_cast<void*>(p), 1, n, f32 ? 1u : 0u} : PfView{const_cast<void*>(p), pf.width, 1, f32 ? 1u : 0u};
+	}
+	// backward_backward_input's dL_dinput needs the encoding's second derivative: none is implemented for the spherical
+	// harmonics (nor has tcnn's SphericalHarmonicsEncoding a backward_backward_input)
+	void check_bbi_sh(const float* dL_dinput) const {
+		if (dL_dinput && pf_has_sh())
+			throw std::runtime_error("backward_backward_input: dL_dinput is not supported with a SphericalHarmonics segment (the second "
+			                         "derivative of the spherical harmonics is not implemented); dL_ddLdoutput and the parameter gradients are");
 	}
 	float* ddx_scratch() { ddx_partial.alloc((size_t)3 * core.lay.L * capacity); return ddx_partial.p; }
 	// backward_backward_input's dL_ddLdoutput / dL_dinput of a network: the fronts / backs chain has no act'' term, so they
@@ -3408,16 +3427,117 @@ int neus_module_create_nerf_network(const char* config_json, uint32_t batch_capa
 	});
 }
 
+// tcnn's parameter-free encodings from their config (encoding.cu create_encoding; identity.h, frequency.h,
+// spherical_harmonics.h, composite.h): one segment, or a Composite's nested encodings over consecutive input dims (the
+// last may leave n_dims_to_encode out and takes the rest). Host only: every check runs before a device call.
+static bool pf_otype(const std::string& ot) { return ot == "Identity" || ot == "Frequency" || ot == "SphericalHarmonics" || ot == "Composite"; }
+static void pf_add_segment(PfEnc& E, const JsonValue& j, const std::string& ot, uint32_t dims) {
+	if (E.n_seg == PF_MAX_SEGMENTS) throw std::runtime_error("Composite: at most 8 nested encodings");
+	if (dims == 0) throw std::runtime_error(ot + ": at least 1 input dim to encode");
+	PfSegment g{};
+	g.in0 = E.n_in; g.dims = dims; g.out0 = E.width; g.scale = 1.f; g.offset = 0.f;
+	uint32_t w = dims;
+	if (ot == "SphericalHarmonics") {
+		const double deg = j.number("degree", 4);
+		if (deg < 1) throw std::runtime_error("SH encoding must have positive degree.");
+		if (deg > 8) throw std::runtime_error("The SH encoding is only implemented up to degree 8, but got " + std::to_string((long)deg));
+		if (dims != 3) throw std::runtime_error("SphericalHarmonics: can only encode 3 input dims (a direction), but got " + std::to_string(dims));
+		g.type = PF_SH; g.param = (uint32_t)deg; w = g.param * g.param;
+	} else if (ot == "Frequency") {
+		const double nf = j.number("n_frequencies", 12);
+		if (nf < 1 || nf > 16) throw std::runtime_error("Frequency: n_frequencies must be in 1..16 on gfx950");
+		g.type = PF_FREQUENCY; g.param = (uint32_t)nf; w = 2 * dims * g.param;
+	} else {
+		g.type = PF_IDENTITY; g.scale = (float)j.number("scale", 1.0); g.offset = (float)j.number("offset", 0.0);
+	}
+	E.seg[E.n_seg++] = g;
+	E.n_in += dims; E.width += w;
+}
+static PfEnc pf_from_json(const JsonValue& j, uint32_t n_input_dims) {
+	if (n_input_dims == 0 || n_input_dims > (1u << 16)) throw std::runtime_error("encoding module: n_input_dims must be in 1..65536");
+	PfEnc E{};
+	const std::string ot = j.string("otype", "");
+	if (ot != "Composite") { pf_add_segment(E, j, ot, n_input_dims); return E; }
+	if (!j.has("nested") || j.at("nested").kind != JsonValue::Array || j.at("nested").arr.empty())
+		throw std::runtime_error("Composite: 'nested' must be a non-empty array of encodings");
+	const std::vector<JsonValue>& nested = j.at("nested").arr;
+	for (size_t i = 0; i < nested.size(); ++i) {
+		const JsonValue& e = nested[i];
+		if (e.kind != JsonValue::Object) throw std::runtime_error("Composite: 'nested' must be a non-empty array of encodings");
+		const std::string eo = e.string("otype", "");
+		if (eo != "Identity" && eo != "Frequency" && eo != "SphericalHarmonics")
+			throw std::runtime_error("Composite: nested encodings must be Identity, Frequency or SphericalHarmonics");
+		uint32_t dims = 0;
+		if (e.has("n_dims_to_encode")) {
+			const double d = e.number("n_dims_to_encode", 0);
+			if (d < 1 || d > (double)n_input_dims) throw std::runtime_error("Composite: n_dims_to_encode must be in 1..n_input_dims");
+			dims = (uint32_t)d;
+		} else if (i + 1 == nested.size() && E.n_in < n_input_dims) {
+			dims = n_input_dims - E.n_in;
+		} else {
+			throw std::runtime_error("Composite: only the last nested encoding may omit n_dims_to_encode (it takes the remaining dims)");
+		}
+		pf_add_segment(E, e, eo, dims);
+	}
+	if (E.n_in != n_input_dims)
+		throw std::runtime_error("Composite: the nested encodings' n_dims_to_encode sum to " + std::to_string(E.n_in) + ", but n_input_dims is " +
+		                         std::to_string(n_input_dims));
+	return E;
+}
+// the accepted config back as JSON members (no braces): the otype with its own keys, nested types included
+static std::string pf_hyper_segment(const PfSegment& g) {
+	if (g.type == PF_SH) return "\"otype\": \"SphericalHarmonics\", \"degree\": " + std::to_string(g.param);
+	if (g.type == PF_FREQUENCY) return "\"otype\": \"Frequency\", \"n_frequencies\": " + std::to_string(g.param);
+	return "\"otype\": \"Identity\", \"scale\": " + fmt_float(g.scale) + ", \"offset\": " + fmt_float(g.offset);
+}
+static std::string pf_hyper_members(const PfEnc& E, bool composite) {
+	if (!composite) return pf_hyper_segment(E.seg[0]);
+	std::string s = "\"otype\": \"Composite\", \"nested\": [";
+	for (uint32_t q = 0; q < E.n_seg; ++q)
+		s += std::string(q ? ", " : "") + "{\"n_dims_to_encode\": " + std::to_string(E.seg[q].dims) + ", " + pf_hyper_segment(E.seg[q]) + "}";
+	return s + "]";
+}
+// create_encoding with a parameter-free encoding: any n_input_dims, any n <= batch_capacity, output [n][width] (AoS) or
+// [width][n] (SoA) in the requested precision, unpadded; no parameters (null params / dL_dparams are fine)
+static NeusModule* make_pf_module(uint32_t n_input_dims, const JsonValue& j, int requested_precision, uint32_t batch_capacity) {
+	if (batch_capacity == 0 || batch_capacity % 128 != 0 || batch_capacity > (1u << 24))
+		throw std::runtime_error("batch_capacity must be a positive multiple of 128 (<= 2^24)");
+	if (requested_precision != NEUS_PRECISION_FP32 && requested_precision != NEUS_PRECISION_FP16)
+		throw std::runtime_error("create_encoding: requested_precision must be NEUS_PRECISION_FP32 or NEUS_PRECISION_FP16");
+	const PfEnc E = pf_from_json(j, n_input_dims);
+	const std::string ol = j.string("output_layout", "AoS");
+	if (ol == "paired") throw std::runtime_error("parameter-free encoding: output_layout AoS or SoA (paired is the HashGrid kernels' layout)");
+	int dev = 0;
+	HIP_CHECK(hipGetDevice(&dev));
+	auto m = std::make_unique<NeusModule>(dev);
+	m->kind = NeusModule::PfEncoding;
+	module_options(m.get(), j);
+	m->f32 = requested_precision == NEUS_PRECISION_FP32;
+	m->pf = E;
+	m->n_in = E.n_in; m->n_out = E.width;
+	m->capacity = batch_capacity;
+	m->hyper = "{" + pf_hyper_members(E, j.string("otype", "") == "Composite") + ", \"n_input_dims\": " + std::to_string(E.n_in) +
+	           ", \"output_layout\": \"" + (m->layout == ENC_LAYOUT_SOA ? "SoA" : "AoS") + "\", \"gradient_precision\": \"" +
+	           (m->grad_fp16 ? "fp16" : "fp32") + "\", \"precision\": \"" + (m->f32 ? "fp32" : "fp16") + "\"}";
+	HIP_CHECK(hipStreamSynchronize(m->core.stream));
+	return m.release();
+}
+
 int neus_module_create_encoding(uint32_t n_input_dims, const char* encoding_json, int requested_precision, uint32_t batch_capacity,
                                 NeusModule** out) {
 	return guard([&] {
 		if (!encoding_json || !out) throw std::runtime_error("neus_module_create_encoding: null argument");
+		const JsonValue j = parse_json(encoding_json);
+		const std::string ot = j.string("otype", "HashGrid");
+		if (pf_otype(ot)) {
+			*out = make_pf_module(n_input_dims, j, requested_precision, batch_capacity);
+			return;
+		}
 		if (n_input_dims != 3) throw std::runtime_error("HashGrid module: n_input_dims must be 3");
 		if (batch_capacity == 0 || batch_capacity % 128 != 0 || batch_capacity > (1u << 24))
 			throw std::runtime_error("batch_capacity must be a positive multiple of 128 (<= 2^24)");
-		const JsonValue j = parse_json(encoding_json);
-		const std::string ot = j.string("otype", "HashGrid");
-		if (ot != "HashGrid" && ot != "Grid") throw std::runtime_error("encoding module: only HashGrid is implemented on gfx950");
+		if (ot != "HashGrid" && ot != "Grid")
+			throw std::runtime_error("encoding module: HashGrid, Identity, Frequency, SphericalHarmonics and Composite are implemented on gfx950");
 		int dev = 0;
 		HIP_CHECK(hipGetDevice(&dev));
 		auto m = std::make_unique<NeusModule>(dev);
@@ -3456,9 +3576,10 @@ static FfNet ff_from_json(const JsonValue& j, uint32_t n_input_dims, uint32_t n_
 static std::string ff_hyper(const FfNet& f);
 static NeusModule* make_mlp_module(const FfNet& f, const JsonValue& j, uint32_t batch_capacity);
 // create_network_with_input_encoding (cpp_api.h:108; network_with_input_encoding.h): an Identity encoding (any input
-// width; scale / offset) or a HashGrid (3 inputs) in front of a FullyFusedMLP of any depth, width 16 / 32 / 64 / 128 and
-// activations. The HashGrid -> one hidden ReLU layer -> linear network of width 16 / 64 runs on the fused k_dnet kernel;
-// every other HashGrid network is the encoding's kernels composed with ffmlp.hip's layers (GridMlp).
+// width; scale / offset), a Frequency, SphericalHarmonics or Composite encoding (encodings.hip writes the MLP's input rows,
+// EncMlp) or a HashGrid (3 inputs) in front of a FullyFusedMLP of any depth, width 16 / 32 / 64 / 128 and activations.
+// The HashGrid -> one hidden ReLU layer -> linear network of width 16 / 64 runs on the fused k_dnet kernel; every other
+// HashGrid network is the encoding's kernels composed with ffmlp.hip's layers (GridMlp).
 int neus_module_create_network_with_input_encoding(uint32_t n_input_dims, uint32_t n_output_dims, const char* encoding_json,
                                                    const char* network_json, uint32_t batch_capacity, NeusModule** out) {
 	return guard([&] {
@@ -3474,7 +3595,22 @@ int neus_module_create_network_with_input_encoding(uint32_t n_input_dims, uint32
 			*out = make_mlp_module(f, jn, batch_capacity);
 			return;
 		}
-		if (ot != "HashGrid" && ot != "Grid") throw std::runtime_error("network with input encoding: the encoding must be Identity or HashGrid on gfx950");
+		if (pf_otype(ot)) {
+			const PfEnc E = pf_from_json(je, n_input_dims);
+			const FfNet f = ff_from_json(jn, E.width, n_output_dims);
+			NeusModule* m = make_mlp_module(f, jn, batch_capacity);
+			m->kind = NeusModule::EncMlp;
+			m->pf = E;
+			m->n_in = E.n_in;
+			m->hyper = "{\"otype\": \"NetworkWithInputEncoding\", \"encoding\": {" + pf_hyper_members(E, ot == "Composite") + "}, \"network\": " +
+			           ff_hyper(f) + ", \"n_input_dims\": " + std::to_string(E.n_in) + ", \"n_output_dims\": " + std::to_string(f.n_out) +
+			           ", \"gradient_precision\": \"" + (m->grad_fp16 ? "fp16" : "fp32") + "\"}";
+			*out = m;
+			return;
+		}
+		if (ot != "HashGrid" && ot != "Grid")
+			throw std::runtime_error("network with input encoding: the encoding must be Identity, Frequency, SphericalHarmonics, Composite or "
+			                         "HashGrid on gfx950");
 		if (n_input_dims != 3) throw std::runtime_error("network with input encoding: a HashGrid encodes 3 input dims");
 		int dev = 0;
 		HIP_CHECK(hipGetDevice(&dev));
@@ -3683,7 +3819,9 @@ int neus_module_info(const NeusModule* m, NeusModuleInfo* o) {
 		o->batch_capacity = m->capacity;
 		o->n_levels = m->core.lay.L;
 		o->grid_offset = m->kind == NeusModule::Network ? m->core.lay.grid_off : (m->kind == NeusModule::DensityNet ? m->n_mlp : 0);
-		if (m->kind == NeusModule::Mlp) { o->n_levels = 0; o->grid_offset = m->ff.P; }  // no encoding parameters
+		if (m->kind == NeusModule::Mlp || m->kind == NeusModule::EncMlp || m->kind == NeusModule::PfEncoding) {  // no encoding parameters
+			o->n_levels = 0; o->grid_offset = (uint32_t)m->n_params();
+		}
 		if (m->kind == NeusModule::GridMlp) o->grid_offset = m->ff.P;
 		o->per_level_scale = m->core.cfg.per_level_scale;
 	});
@@ -3702,12 +3840,13 @@ int neus_module_set_indeed_batch_size(NeusModule* m, uint32_t n) { return guard(
 
 int neus_module_initialize_params(NeusModule* m, uint64_t seed, float* params_full_precision) {
 	return guard([&] {
-		if (!m || !params_full_precision) throw std::runtime_error("neus_module_initialize_params: null argument");
+		if (!m || (!params_full_precision && m->n_params())) throw std::runtime_error("neus_module_initialize_params: null argument");
+		if (m->n_params() == 0) return;  // a parameter-free encoding
 		HIP_CHECK(hipSetDevice(m->core.device));
 		std::vector<float> h;
 		// cpp::Module::initialize_params draws from pcg32{seed} (cpp_api.cu:162-165; the Trainer's seed_seq is not involved)
-		if (m->kind == NeusModule::Mlp) {
-			// NetworkWithInputEncoding::initialize_params: Identity has none; FullyFusedMLP::initialize_params
+		if (m->kind == NeusModule::Mlp || m->kind == NeusModule::EncMlp) {
+			// NetworkWithInputEncoding::initialize_params: Identity (and every other parameter-free encoding) has none; FullyFusedMLP::initialize_params
 			// (fully_fused_mlp.cu:1229-1256): every matrix xavier-uniform in order, U(+-sqrt(6 / (fan_in + fan_out)))
 			// (gpu_matrix.h:292-306) from pcg32{seed} (cpp_api.cu:162-165)
 			h.assign(m->ff.P, 0.f);
@@ -3762,6 +3901,22 @@ static void module_forward(NeusModule* m, hipStream_t s, uint32_t n, const float
 		if (!params) throw std::runtime_error("module: null params");
 		if (ctx) ctx->acts.alloc(std::max<size_t>(1, m->ff.acts_halves(n)));
 		ff_forward(m->ff, s, n, input, params, ctx ? ctx->acts.p : m->ff_acts.p, (half_t*)output);
+		HIP_CHECK(hipGetLastError());
+		return;
+	}
+	if (m->kind == NeusModule::PfEncoding) {
+		launch_pf_out(s, m->pf, n, input, nullptr, m->pf_view(output, n));
+		HIP_CHECK(hipGetLastError());
+		return;
+	}
+	if (m->kind == NeusModule::EncMlp) {
+		// NetworkWithInputEncoding::forward: the encoding straight into the FullyFusedMLP's fp16 input rows (padded to 16 with
+		// ones, as tcnn's encodings pad), then the layers
+		if (!params) throw std::runtime_error("module: null params");
+		half_t* acts = m->ff_acts.p;
+		if (ctx) { ctx->acts.alloc(std::max<size_t>(1, m->ff.acts_halves(n))); acts = ctx->acts.p; }
+		launch_pf_rows(s, m->pf, n, input, nullptr, acts, m->ff.in_pad);
+		ff_forward(m->ff, s, n, nullptr, params, acts, (half_t*)output);
 		HIP_CHECK(hipGetLastError());
 		return;
 	}
@@ -3859,8 +4014,29 @@ int neus_module_backward(NeusModule* m, void* stream, const NeusContext* ctx, ui
 		StreamSwap sw(m->core, stream);
 		NeusTestbed& t = m->core;
 		hipStream_t s = t.stream;
-		float* g = m->grad_target(dL_dparams, gradient_mode);
+		float* g = m->n_params() ? m->grad_target(dL_dparams, gradient_mode) : nullptr;
 		if (!g && !dL_dinput) return;
+		if (m->kind == NeusModule::PfEncoding) {  // dL_dinput = J^T dL_doutput, the Jacobian recomputed from the input
+			launch_pf_input_grad(s, m->pf, n, input, m->pf_view(dL_doutput, n), nullptr, dL_dinput);
+			HIP_CHECK(hipGetLastError());
+			return;
+		}
+		if (m->kind == NeusModule::EncMlp) {
+			// NetworkWithInputEncoding::backward: the FullyFusedMLP's backward (weight gradients, dL/dX0 as fp16 rows), then the
+			// encoding's J^T on it
+			const FfNet& f = m->ff;
+			if (!params) throw std::runtime_error("module: null params");
+			if (!ctx->acts.p) throw std::runtime_error("module backward: the context is not from this module's forward");
+			if (f.out_act != FF_NONE && !output) throw std::runtime_error("FullyFusedMLP backward: the forward output is needed for its output activation");
+			const half_t* dX0 = ff_backward_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, (const half_t*)output, g != nullptr);
+			if (dL_dinput) launch_pf_input_grad(s, m->pf, n, input, PfView{const_cast<half_t*>(dX0), f.in_pad, 1, 0u}, nullptr, dL_dinput);
+			if (g) {
+				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
+				m->finish_grad(dL_dparams, gradient_mode, s);
+			}
+			HIP_CHECK(hipGetLastError());
+			return;
+		}
 		if (m->kind == NeusModule::Mlp) {
 			// FullyFusedMLP::backward_impl (fully_fused_mlp.cu:967-1085): the output activation's backward on dL/doutput, the
 			// deltas through the hidden layers (activation derivative from the stored outputs), dW = D^T x per layer and
@@ -4000,6 +4176,51 @@ int neus_module_backward_backward_input(NeusModule* m, void* stream, const NeusC
 			const FfNet& f = m->ff;
 			launch_ff_input(s, n, f.n_in, f.in_pad, dL_ddLdinput, f.in_scale, 0.f, m->ff_front.p, true);
 			ff_bbi_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, g != nullptr, (half_t*)dL_ddLdoutput);
+			if (g) {
+				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
+				m->finish_grad(dL_dparams, gradient_mode, s);
+			}
+			HIP_CHECK(hipGetLastError());
+			return;
+		}
+		if (m->kind == NeusModule::PfEncoding) {
+			// dL_ddLdoutput = J u (first derivatives only); dL_dinput_d = u_d sum_k dL_doutput_k d2y_k/dx_d^2 (every feature
+			// depends on one input dim, except the spherical harmonics': refused)
+			if (!ctx || ctx->n != n) throw std::runtime_error("backward_backward_input: needs the forward's context");
+			if (!input || !dL_ddLdinput || (dL_dinput && !dL_doutput)) throw std::runtime_error("backward_backward_input: null input");
+			m->check_n(n, true);
+			m->check_bbi_sh(dL_dinput);
+			HIP_CHECK(hipSetDevice(m->core.device));
+			StreamSwap sw(m->core, stream);
+			hipStream_t s = m->core.stream;
+			if (dL_dinput) launch_pf_input_grad(s, m->pf, n, input, m->pf_view(dL_doutput, n), dL_ddLdinput, dL_dinput);
+			if (dL_ddLdoutput) launch_pf_out(s, m->pf, n, input, dL_ddLdinput, m->pf_view(dL_ddLdoutput, n));
+			HIP_CHECK(hipGetLastError());
+			return;
+		}
+		if (m->kind == NeusModule::EncMlp) {
+			// NetworkWithInputEncoding::backward_backward_input composed as GridMlp composes the HashGrid: the front J_enc u goes
+			// through the FullyFusedMLP's backward_backward_input (fully_fused_mlp.cu:1088-1198); dL_dinput is the encoding's own
+			// second-derivative term with the network's dL/dX0 as its dL_doutput (the MLP's part is 0: act'' = 0)
+			if (!ctx || ctx->n != n || !ctx->acts.p) throw std::runtime_error("backward_backward_input: needs the forward's context");
+			if (!input || !dL_ddLdinput || !dL_doutput || !params) throw std::runtime_error("backward_backward_input: null input");
+			m->check_n(n, true);
+			m->check_bbi_exact(dL_ddLdoutput, dL_dinput);
+			m->check_bbi_sh(dL_dinput);
+			HIP_CHECK(hipSetDevice(m->core.device));
+			StreamSwap sw(m->core, stream);
+			hipStream_t s = m->core.stream;
+			float* g = m->grad_target(dL_dparams, gradient_mode);
+			if (!g && !dL_ddLdoutput && !dL_dinput) return;
+			const FfNet& f = m->ff;
+			if (dL_dinput) {
+				const half_t* dX0 = ff_backward_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, nullptr, false);
+				launch_pf_input_grad(s, m->pf, n, input, PfView{const_cast<half_t*>(dX0), f.in_pad, 1, 0u}, dL_ddLdinput, dL_dinput);
+			}
+			if (g || dL_ddLdoutput) {
+				launch_pf_rows(s, m->pf, n, input, dL_ddLdinput, m->ff_front.p, f.in_pad);
+				ff_bbi_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, g != nullptr, (half_t*)dL_ddLdoutput);
+			}
 			if (g) {
 				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
 				m->finish_grad(dL_dparams, gradient_mode, s);

@@ -50,7 +50,9 @@ class Module:
     [n, padded output] fp16), 'network' = the NeuS NerfNetwork (input [n, 7] f32, output [n, 16] fp16),
     'encoding' = the HashGrid encoding (input [n, 3] f32; output layout by the config's "output_layout": "AoS" [n, 2L]
     (default: the column-major view cpp::Module gives its caller, cpp_api.cu:58-70), "SoA" [2L, n] (GridEncoding's
-    preferred layout, grid.h:2357-2359) or "paired" [L, n, 2] (this build's kernels)). dL_dparams is fp16 (tcnn's param
+    preferred layout, grid.h:2357-2359) or "paired" [L, n, 2] (this build's kernels)), or a parameter-free encoding
+    (Identity, Frequency, SphericalHarmonics, Composite: input [n, n_input_dims] f32, output "AoS" [n, w] or "SoA" [w, n],
+    unpadded, n_params 0: `params` and `dL_dparams` may be empty tensors or None). dL_dparams is fp16 (tcnn's param
     precision) unless the config says "gradient_precision": "fp32"."""
 
     def __init__(self, handle, kind):
@@ -85,13 +87,17 @@ class Module:
 
     @classmethod
     def create_network_with_input_encoding(cls, n_input_dims, n_output_dims, encoding, network, batch_capacity=1 << 18):
-        """tcnn create_network_with_input_encoding (cpp_api.h:108; network_with_input_encoding.h): `encoding` HashGrid or
-        Identity ({"scale", "offset"}, identity.h), `network` a FullyFusedMLP of any depth / width (16..128) / activation.
+        """tcnn create_network_with_input_encoding (cpp_api.h:108; network_with_input_encoding.h): `encoding` HashGrid,
+        Identity ({"scale", "offset"}, identity.h), Frequency ({"n_frequencies": 1..16}), SphericalHarmonics ({"degree": 1..8},
+        3 dims) or Composite ({"nested": [{"n_dims_to_encode", ...}, ...]} of the last three; encoded width <= 128, padded to
+        16 with ones), `network` a FullyFusedMLP of any depth / width (16..128) / activation.
         Params [network matrices in order | grid] (network first, as NetworkWithInputEncoding's set_params_impl,
         network_with_input_encoding.h:262-270); output [n, padded n_output_dims] fp16; the grid's output is zero-padded to
         a multiple of 16 (grid.h:1540-1550). HashGrid -> one hidden ReLU layer with a linear output of <= 16 dims runs as
         the fused DensityNet kernel, anything else as the grid kernels feeding ffmlp.hip's MFMA layers;
-        backward_backward_input as network_with_input_encoding.h:159-250."""
+        backward_backward_input as network_with_input_encoding.h:159-250. The parameter-free encodings have no parameters
+        of their own (params = the network matrices); with a SphericalHarmonics segment backward_backward_input gives no
+        dL_dinput (an error)."""
         te = encoding if isinstance(encoding, str) else json.dumps(encoding)
         tn = network if isinstance(network, str) else json.dumps(network)
         h = C.c_void_p()
@@ -102,7 +108,9 @@ class Module:
     @classmethod
     def create_encoding(cls, encoding, batch_capacity=1 << 18, n_input_dims=3, requested_precision=Precision.Fp16):
         """tcnn create_encoding(n_input_dims, encoding, requested_precision) (cpp_api.h:110; cpp_api.cu:174-180): Fp16 =
-        GridEncoding<__half> (fp16 params / output), Fp32 = GridEncoding<float> (f32 params, output and gradients)."""
+        GridEncoding<__half> (fp16 params / output), Fp32 = GridEncoding<float> (f32 params, output and gradients).
+        `encoding` may also be Identity, Frequency, SphericalHarmonics or a Composite of them, on any n_input_dims and any
+        n >= 1: no parameters, output and dL_doutput in the requested precision, "output_layout" AoS or SoA."""
         text = encoding if isinstance(encoding, str) else json.dumps(encoding)
         h = C.c_void_p()
         check(lib().neus_module_create_encoding(C.c_uint32(n_input_dims), text.encode(), C.c_int(int(Precision(requested_precision))),
@@ -161,6 +169,9 @@ class Module:
         if self.kind != "encoding":
             return (n, 16)
         L = self.info["n_levels"]
+        if L == 0:  # a parameter-free encoding: unpadded width
+            w = self.n_output_dims
+            return {"AoS": (n, w), "SoA": (w, n)}[self.output_layout]
         return {"AoS": (n, 2 * L), "SoA": (2 * L, n), "paired": (L, n, 2)}[self.output_layout]
 
     def gradient_buffer(self):
@@ -192,7 +203,8 @@ class Module:
                                 mode=GradientMode.Overwrite, dL_dinput=None):
         """With S = dL_ddLdinput . dL/dx: dL_dparams = dS/dparams, dL_ddLdoutput = dS/d(dL_doutput) (the output's shape and
         precision) and dL_dinput = dS/dx ([n, n_input_dims] f32), each written only when given. The last two are provided
-        for hidden activation ReLU / None with a linear output (an error otherwise)."""
+        for hidden activation ReLU / None with a linear output (an error otherwise); dL_dinput is not provided with a
+        SphericalHarmonics segment in the encoding (an error: no second derivative of it is implemented)."""
         if self.kind == "network":
             raise NeusError("backward_backward_input: the NerfNetwork's second order is inside backward")
         check(lib().neus_module_backward_backward_input(self._h, _stream(), ctx._h, C.c_uint32(ctx.n), _p(dL_ddLdinput), _p(x),

@@ -7,8 +7,12 @@ Each class is a torch.nn.Module with one fp32 `params` Parameter. forward(x) tak
 pads B with zero rows to a multiple of 128 (the kernels' batch granularity) and returns [B, n_output_dims]. Autograd is
 complete to second order in the input: `grad(y, x, create_graph=True)` followed by `.backward()` (an eikonal loss) gives
 gradients for `params`, `x` and the first gradient's `grad_outputs`, through neus_module_backward_backward_input. The
-double backward is provided for hidden activation ReLU / None with a linear output (ReLU'' = 0); a cotangent for the
-parameter gradient (a gradient of a gradient in the parameters) is not supported.
+double backward is provided for hidden activation ReLU / None with a linear output (ReLU'' = 0) and for encodings without
+a SphericalHarmonics segment (no second derivative of it is implemented); a cotangent for the parameter gradient (a
+gradient of a gradient in the parameters) is not supported.
+
+Encodings: HashGrid, and the parameter-free Identity, Frequency, SphericalHarmonics and Composite (of those three), whose
+`params` is an empty Parameter.
 
 Two autograd Functions talk to a small backend object (`NativeBackend` over module.Module by default):
     n_params, n_input_dims, n_output_dims (the backend's, possibly padded, output width), param_dtype, output_dtype,
@@ -49,8 +53,11 @@ class NativeBackend:
         self.n_output_dims = self.m.n_output_dims
         fp32 = self.m.precision == "fp32"
         self.param_dtype = self.output_dtype = torch.float32 if fp32 else torch.float16
-        net = self.m.hyperparams().get("network")
-        self.supports_double_backward = net is None or (net["activation"] in ("ReLU", "None") and net["output_activation"] == "None")
+        hp = self.m.hyperparams()
+        net, enc = hp.get("network"), hp.get("encoding", hp)
+        has_sh = any(e.get("otype") == "SphericalHarmonics" for e in [enc] + list(enc.get("nested", [])))
+        self.supports_double_backward = not has_sh and (
+            net is None or (net["activation"] in ("ReLU", "None") and net["output_activation"] == "None"))
 
     def with_capacity(self, n):
         if n <= self.batch_capacity:
@@ -64,13 +71,15 @@ class NativeBackend:
         return self.m.inference(x, p)
 
     def fwd(self, x, p, prepare_input_gradients):
-        return self.m.forward(x, p, prepare_input_gradients=prepare_input_gradients)
+        ctx, y = self.m.forward(x, p, prepare_input_gradients=prepare_input_gradients)
+        ctx.output = y  # the backward of an output activation other than None needs the forward's output
+        return ctx, y
 
     def bwd(self, ctx, x, p, dL_dy, want_dx, want_dparams):
         dx = torch.empty((x.shape[0], self.n_input_dims), dtype=torch.float32, device=x.device) if want_dx else None
         dp = torch.empty(self.n_params, dtype=torch.float32, device=x.device) if want_dparams else None
         mode = _module.GradientMode.Overwrite if want_dparams else _module.GradientMode.Ignore
-        self.m.backward(ctx, x, dL_dy, p, dL_dparams=dp, dL_dinput=dx, mode=mode)
+        self.m.backward(ctx, x, dL_dy, p, dL_dparams=dp, dL_dinput=dx, mode=mode, output=getattr(ctx, "output", None))
         return dx, dp
 
     def bwd_bwd_input(self, ctx, x, p, u, dL_dy, want_dparams, want_ddLdy, want_dx):
@@ -130,7 +139,8 @@ class _Backward(torch.autograd.Function):
         be = ctx.be
         if not be.supports_double_backward:
             raise RuntimeError("double backward is not supported for this network: it is provided for hidden activation ReLU or None "
-                               "with output activation None (no second derivative of another activation is implemented)")
+                               "with output activation None (no second derivative of another activation is implemented) and for "
+                               "encodings without a SphericalHarmonics segment")
         x, p, g = ctx.saved_tensors
         dp, ddy, dx = be.bwd_bwd_input(ctx.nctx, x, p, u.detach().float().contiguous(), g, want_p, want_g, want_x)
         inv = 1.0 / ctx.loss_scale
@@ -201,8 +211,9 @@ def _text(cfg):
 
 
 class Encoding(Module):
-    """Encoding(n_input_dims, encoding_config, seed=1337, dtype=None): the HashGrid. dtype None / torch.float16: fp16
-    table and output (loss_scale 128); torch.float32: the fp32 encoding (loss_scale 1)."""
+    """Encoding(n_input_dims, encoding_config, seed=1337, dtype=None): the HashGrid, or a parameter-free Identity /
+    Frequency / SphericalHarmonics / Composite encoding (`params` is then empty). dtype None / torch.float16: fp16 table
+    and output (loss_scale 128); torch.float32: the fp32 encoding (loss_scale 1)."""
 
     def __init__(self, n_input_dims, encoding_config, seed=1337, dtype=None):
         if dtype not in (None, torch.float16, torch.float32):
@@ -235,8 +246,9 @@ class Network(Module):
 
 
 class NetworkWithInputEncoding(Module):
-    """NetworkWithInputEncoding(n_input_dims, n_output_dims, encoding_config, network_config, seed=1337): a HashGrid (or
-    Identity) encoding in front of a FullyFusedMLP, as one module with parameters [network | grid]."""
+    """NetworkWithInputEncoding(n_input_dims, n_output_dims, encoding_config, network_config, seed=1337): a HashGrid,
+    Identity, Frequency, SphericalHarmonics or Composite encoding in front of a FullyFusedMLP, as one module with
+    parameters [network | grid] (the network alone for the parameter-free encodings)."""
 
     def __init__(self, n_input_dims, n_output_dims, encoding_config, network_config, seed=1337):
         self.encoding_config = _text(encoding_config)
