@@ -475,6 +475,17 @@ int neus_debug_host_group_allreduce(NeusHostGroup* group, void* host, uint64_t n
  *                                (cpp_api.h:110, cpp_api.cu:174-180): NEUS_PRECISION_FP16 = GridEncoding<__half> (the
  *                                kernels of the training step), NEUS_PRECISION_FP32 = GridEncoding<float>: params, output,
  *                                dL_doutput, dL_ddLdoutput and dL_dparams f32 (AoS / SoA layouts).
+ *                                The general grid (grid_nd.hip) serves every other grid config: "otype" HashGrid / Grid
+ *                                with "type": "Hash" (default) | "Dense" | "Tiled", or DenseGrid / TiledGrid; n_input_dims
+ *                                2, 3 or 4; "n_features_per_level" F = 1, 2, 4 or 8; "interpolation": "Linear" (default) |
+ *                                "Smoothstep" ("Nearest" and "stochastic_interpolation": true are refused); n_levels or
+ *                                n_features / F, at most 16 levels; a Dense table over 2^31 entries is refused. Params
+ *                                [level][entry][F] in the requested precision, output [n][F L] ("AoS") or [F L][n] ("SoA";
+ *                                "paired" is refused), any n >= 1. The 3-dim, 2-feature, Hash, Linear config keeps the
+ *                                kernels above unless it says "implementation": "general" (default "auto"). All arithmetic
+ *                                is fp32 and an fp16 module rounds its output once (the reference accumulates in fp16);
+ *                                dL_dparams is a float-atomic sum (not bitwise repeatable), everything else is; with
+ *                                Smoothstep backward_backward_input's dL_dinput carries the diagonal second derivatives.
  *                                Or a parameter-free encoding (encodings.hip) on any n_input_dims and any n >= 1:
  *                                {"otype": "Identity", "scale", "offset"}, {"otype": "Frequency", "n_frequencies": 1..16}
  *                                (output 2 D F), {"otype": "SphericalHarmonics", "degree": 1..8} (3 dims, output degree^2)
@@ -530,7 +541,10 @@ int neus_module_create_encoding(uint32_t n_input_dims, const char* encoding_json
  * above for the activations these two are provided for). A Frequency, SphericalHarmonics or Composite encoding (as
  * create_encoding's; encoded width <= 128) is written straight into the MLP's fp16 input rows, padded to 16 with ones; params
  * are the network matrices alone; dL_dinput of backward_backward_input is the encoding's second-derivative term of dL/d(its
- * output) (an error with a SphericalHarmonics segment). */
+ * output) (an error with a SphericalHarmonics segment). A general grid (see create_encoding: 2..4 dims, 1 / 2 / 4 / 8
+ * features, Dense / Tiled, Smoothstep, or "implementation": "general"; encoded width F L <= 128) is likewise written straight
+ * into the MLP's fp16 input rows, padded to 16 with zeros; params [network matrices | grid], grid_offset = the network's size;
+ * the fused one-hidden-layer kernel is not taken. */
 int neus_module_create_network_with_input_encoding(uint32_t n_input_dims, uint32_t n_output_dims, const char* encoding_json,
                                                    const char* network_json, uint32_t batch_capacity, NeusModule** out);
 int neus_module_destroy(NeusModule* m);

@@ -494,6 +494,25 @@ void launch_grid_ddx(hipStream_t s, uint32_t n, uint32_t ld, const float* coords
                      const half_t* g, const float* ddx, float* partial, float* dLdx);
 void launch_grid_f32_ddx(hipStream_t s, uint32_t n, const GridLevels& gl, uint32_t valid_level, const float* coords, const float* table,
                          const float* dLdy, uint32_t layout, const float* ddx, float* partial, float* dLdx);
+// The general grid encoding (grid_nd.hip): 2..4 input dims, 1 / 2 / 4 / 8 features per level, Hash / Dense / Tiled tables
+// [level][entry][F] (gl.offset in entries), Linear or Smoothstep interpolation. Caller tensors (output, dL_doutput,
+// dL_ddLdoutput) are PfViews: stand-alone AoS / SoA in either precision, or a FullyFusedMLP's fp16 rows [n][in_pad] with
+// `pad` zero columns after the F L features.
+enum : uint32_t { GRID_ND_HASH = 0, GRID_ND_DENSE = 1, GRID_ND_TILED = 2 };
+struct GridNd { GridLevels gl; uint32_t D, F, type, smooth; };
+GridNd make_grid_nd(uint32_t D, uint32_t F, uint32_t type, bool smooth, uint32_t n_levels, uint32_t log2_hashmap_size, uint32_t base_resolution,
+                    float per_level_scale);
+void launch_grid_nd_forward(hipStream_t s, uint32_t n, const GridNd& G, uint32_t valid_level, const float* coords, const void* table,
+                            bool table_f32, const PfView& out, uint32_t pad);
+// grads (fp32, zeroed by the caller) += the first-order gradient, by float atomics
+void launch_grid_nd_backward(hipStream_t s, uint32_t n, const GridNd& G, uint32_t valid_level, const float* coords, const PfView& dLdy, float* grads);
+// dLdx [n][D] = J^T dLdy, overwritten; partial = scratch of D n_levels n floats
+void launch_grid_nd_input_grad(hipStream_t s, uint32_t n, const GridNd& G, uint32_t valid_level, const float* coords, const void* table,
+                               bool table_f32, const PfView& dLdy, float* partial, float* dLdx);
+// backward_backward_input with ddx = dL_ddLdinput [n][D]: grads += the second-order gradient (null: skipped), ddLdy = J ddx
+// (ddLdy.p null: skipped), dLdx [n][D] overwritten (null: skipped; needs partial)
+void launch_grid_nd_bbi(hipStream_t s, uint32_t n, const GridNd& G, uint32_t valid_level, const float* coords, const void* table, bool table_f32,
+                        const float* ddx, const PfView& dLdy, float* grads, const PfView& ddLdy, uint32_t pad, float* partial, float* dLdx);
 // paired [L][n] <-> sample rows [n][ld] (features in columns [0, 2L), zero padding up to ld): a FullyFusedMLP's input
 void launch_enc_to_rows(hipStream_t s, uint32_t n, uint32_t L, const uint32_t* paired, half_t* rows, uint32_t ld);
 void launch_enc_from_rows(hipStream_t s, uint32_t n, uint32_t L, const half_t* rows, uint32_t ld, uint32_t* paired);

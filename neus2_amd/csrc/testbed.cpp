@@ -3270,8 +3270,12 @@ struct NeusModule {
 	// GridMlp: NetworkWithInputEncoding(HashGrid -> any FullyFusedMLP), composed of the encoding kernels and ffmlp.hip's layers
 	// PfEncoding: a parameter-free encoding (Identity, Frequency, SphericalHarmonics or a Composite of them), encodings.hip
 	// EncMlp: NetworkWithInputEncoding(such an encoding -> any FullyFusedMLP): encodings.hip writes the MLP's input rows
-	enum Kind { Network = 0, Encoding = 1, DensityNet = 2, Mlp = 3, GridMlp = 4, PfEncoding = 5, EncMlp = 6 } kind;
+	// NdGrid: the general grid encoding (grid_nd.hip: 2..4 dims, 1 / 2 / 4 / 8 features, Hash / Dense / Tiled, Linear / Smoothstep)
+	// NdGridMlp: NetworkWithInputEncoding(such a grid -> any FullyFusedMLP): grid_nd.hip writes the MLP's input rows
+	enum Kind { Network = 0, Encoding = 1, DensityNet = 2, Mlp = 3, GridMlp = 4, PfEncoding = 5, EncMlp = 6, NdGrid = 7, NdGridMlp = 8 } kind;
 	FfNet ff;
+	GridNd nd{};                             // NdGrid, NdGridMlp: the level tables
+	Dev<float> nd_partial;                   // NdGrid, NdGridMlp: dL_dinput's per-level terms [D L][capacity] (first use)
 	PfEnc pf{};                              // PfEncoding, EncMlp: the segments
 	Dev<half_t> ff_acts, ff_front, ff_d[2];  // Mlp: inference activations, backward-backward fronts, delta ping-pong
 	Dev<float> ff_partial, ff_dummy;         // Mlp: per-block weight-gradient rows
@@ -3300,6 +3304,7 @@ struct NeusModule {
 		if (kind == Mlp || kind == EncMlp) return ff.P;
 		if (kind == PfEncoding) return 0;
 		if (kind == GridMlp) return ff.P + core.lay.n_grid;
+		if (kind == NdGrid || kind == NdGridMlp) return (kind == NdGridMlp ? ff.P : 0) + (uint64_t)nd.gl.offset[nd.gl.n_levels] * nd.F;
 		return kind == Network ? core.lay.P : (kind == DensityNet ? n_mlp + core.lay.n_grid : core.lay.n_grid);
 	}
 	uint32_t valid() const { return core.valid_level_at(training_step); }
@@ -3316,7 +3321,7 @@ struct NeusModule {
 		if (n > capacity) throw std::runtime_error("module: n_elements exceeds the module's batch capacity");
 		if (backward && kind == Network && (n == 0 || n % 128 != 0))
 			throw std::runtime_error("module backward: n_elements must be a positive multiple of 128 (fully_fused_mlp.cu:779-781)");
-		if ((kind == Mlp || kind == GridMlp || kind == EncMlp) && n % 128 != 0) throw std::runtime_error("FullyFusedMLP: batch size must be a multiple of 128 (fully_fused_mlp.cu:779-781)");
+		if ((kind == Mlp || kind == GridMlp || kind == EncMlp || kind == NdGridMlp) && n % 128 != 0) throw std::runtime_error("FullyFusedMLP: batch size must be a multiple of 128 (fully_fused_mlp.cu:779-781)");
 	}
 	// the destination of this call's parameter gradients (Overwrite: dL_dparams itself; Accumulate: a scratch buffer)
 	float* grad_target(void* dL_dparams, int mode) {
@@ -3345,6 +3350,14 @@ struct NeusModule {
 			throw std::runtime_error("backward_backward_input: dL_dinput is not supported with a SphericalHarmonics segment (the second "
 			                         "derivative of the spherical harmonics is not implemented); dL_ddLdoutput and the parameter gradients are");
 	}
+	// a caller tensor of the stand-alone general grid (output, dL_doutput, dL_ddLdoutput): AoS [n][F L] or SoA [F L][n]
+	PfView nd_view(const void* p, uint32_t n) const {
+		return layout == ENC_LAYOUT_SOA ? PfView{const_cast<void*>(p), 1, n, f32 ? 1u : 0u} : PfView{const_cast<void*>(p), n_out_nd(), 1, f32 ? 1u : 0u};
+	}
+	uint32_t n_out_nd() const { return nd.F * nd.gl.n_levels; }
+	// the MLP's fp16 rows [n][in_pad] as the general grid's tensor (features in columns [0, F L))
+	PfView nd_rows(const half_t* rows) const { return PfView{const_cast<half_t*>(rows), ff.in_pad, 1, 0u}; }
+	float* nd_scratch() { nd_partial.alloc((size_t)nd.D * nd.gl.n_levels * capacity); return nd_partial.p; }
 	float* ddx_scratch() { ddx_partial.alloc((size_t)3 * core.lay.L * capacity); return ddx_partial.p; }
 	// backward_backward_input's dL_ddLdoutput / dL_dinput of a network: the fronts / backs chain has no act'' term, so they
 	// are exact only where act'' = 0 (hidden ReLU or None) and the output is linear
@@ -3523,6 +3536,52 @@ static NeusModule* make_pf_module(uint32_t n_input_dims, const JsonValue& j, int
 	return m.release();
 }
 
+// The grid otypes and what decides between the existing 3-D kernels and the general grid (grid_nd.hip). Host only.
+static bool grid_otype(const std::string& ot) { return ot == "HashGrid" || ot == "Grid" || ot == "DenseGrid" || ot == "TiledGrid"; }
+struct GridChoice { bool general; uint32_t type; bool smooth; };
+static GridChoice grid_choice(const JsonValue& j, uint32_t n_input_dims) {
+	const std::string ot = j.string("otype", "HashGrid");
+	const std::string ty = j.string("type", ot == "DenseGrid" ? "Dense" : (ot == "TiledGrid" ? "Tiled" : "Hash"));
+	GridChoice c{};
+	if (ty == "Hash") c.type = GRID_ND_HASH;
+	else if (ty == "Dense") c.type = GRID_ND_DENSE;
+	else if (ty == "Tiled" || ty == "Tile") c.type = GRID_ND_TILED;
+	else throw std::runtime_error("grid encoding: type must be Hash, Dense or Tiled, but got '" + ty + "'");
+	const std::string ip = j.string("interpolation", "Linear");
+	if (ip == "Nearest") throw std::runtime_error("grid encoding: interpolation Nearest is not implemented on gfx950 (Linear or Smoothstep)");
+	if (ip != "Linear" && ip != "Smoothstep") throw std::runtime_error("grid encoding: interpolation must be Linear or Smoothstep, but got '" + ip + "'");
+	c.smooth = ip == "Smoothstep";
+	if (j.number("stochastic_interpolation", 0) != 0)
+		throw std::runtime_error("grid encoding: stochastic_interpolation is not implemented on gfx950");
+	const std::string im = j.string("implementation", "auto");
+	if (im != "auto" && im != "general") throw std::runtime_error("grid encoding: implementation must be auto or general");
+	if (n_input_dims < 2 || n_input_dims > 4) throw std::runtime_error("grid encoding: n_input_dims must be 2, 3 or 4, but got " + std::to_string(n_input_dims));
+	const double nf = j.number("n_features_per_level", 2);
+	if (nf != 1 && nf != 2 && nf != 4 && nf != 8) throw std::runtime_error("grid encoding: n_features_per_level must be 1, 2, 4 or 8");
+	c.general = im == "general" || n_input_dims != 3 || nf != 2 || c.type != GRID_ND_HASH || c.smooth;
+	return c;
+}
+// the general grid's tables and progressive-level settings into the module (no Testbed network is set up)
+static void nd_setup_module(NeusModule* m, const JsonValue& j, uint32_t n_input_dims, const GridChoice& gc, uint32_t batch_capacity) {
+	JsonValue none; none.kind = JsonValue::Object;
+	NeusNetworkConfig c = module_config(j, none, none, batch_capacity, true);
+	if (c.n_levels == 0 || c.n_levels > MAX_LEVELS) throw std::runtime_error("grid encoding: 1..16 levels supported");
+	m->nd = make_grid_nd(n_input_dims, c.n_features_per_level, gc.type, gc.smooth, c.n_levels, c.log2_hashmap_size, c.base_resolution, c.per_level_scale);
+	m->core.cfg = c;
+	m->core.lay.L = c.n_levels;
+	m->n_in = n_input_dims;
+}
+static std::string nd_hyper_members(const NeusModule* m) {
+	static const char* tn[3] = {"Hash", "Dense", "Tiled"};
+	const NeusNetworkConfig& c = m->core.cfg;
+	return "\"otype\": \"Grid\", \"type\": \"" + std::string(tn[m->nd.type]) + "\", \"n_input_dims\": " + std::to_string(m->nd.D) + ", \"n_levels\": " +
+	       std::to_string(c.n_levels) + ", \"n_features_per_level\": " + std::to_string(m->nd.F) + ", \"log2_hashmap_size\": " +
+	       std::to_string(c.log2_hashmap_size) + ", \"base_resolution\": " + std::to_string(c.base_resolution) + ", \"per_level_scale\": " +
+	       fmt_float(c.per_level_scale) + ", \"interpolation\": \"" + (m->nd.smooth ? "Smoothstep" : "Linear") + "\", \"valid_level_scale\": " +
+	       fmt_float(c.valid_level_scale) + ", \"base_valid_level_scale\": " + fmt_float(c.base_valid_level_scale) + ", \"base_training_step\": " +
+	       std::to_string(c.base_training_step);
+}
+
 int neus_module_create_encoding(uint32_t n_input_dims, const char* encoding_json, int requested_precision, uint32_t batch_capacity,
                                 NeusModule** out) {
 	return guard([&] {
@@ -3533,11 +3592,36 @@ int neus_module_create_encoding(uint32_t n_input_dims, const char* encoding_json
 			*out = make_pf_module(n_input_dims, j, requested_precision, batch_capacity);
 			return;
 		}
-		if (n_input_dims != 3) throw std::runtime_error("HashGrid module: n_input_dims must be 3");
+		if (!grid_otype(ot))
+			throw std::runtime_error("encoding module: HashGrid / Grid / DenseGrid / TiledGrid, Identity, Frequency, SphericalHarmonics and Composite "
+			                         "are implemented on gfx950");
 		if (batch_capacity == 0 || batch_capacity % 128 != 0 || batch_capacity > (1u << 24))
 			throw std::runtime_error("batch_capacity must be a positive multiple of 128 (<= 2^24)");
-		if (ot != "HashGrid" && ot != "Grid")
-			throw std::runtime_error("encoding module: HashGrid, Identity, Frequency, SphericalHarmonics and Composite are implemented on gfx950");
+		const GridChoice gc = grid_choice(j, n_input_dims);
+		if (gc.general) {
+			// the general grid (grid_nd.hip): any n <= batch_capacity, output [n][F L] (AoS) or [F L][n] (SoA) in the requested
+			// precision; every check runs before a device call
+			if (requested_precision != NEUS_PRECISION_FP32 && requested_precision != NEUS_PRECISION_FP16)
+				throw std::runtime_error("create_encoding: requested_precision must be NEUS_PRECISION_FP32 or NEUS_PRECISION_FP16");
+			if (j.string("output_layout", "AoS") == "paired")
+				throw std::runtime_error("general grid encoding: output_layout AoS or SoA (paired is the 3-D, 2-feature fp16 kernels' layout)");
+			int dev = 0;
+			HIP_CHECK(hipGetDevice(&dev));
+			auto m = std::make_unique<NeusModule>(dev);
+			m->kind = NeusModule::NdGrid;
+			module_options(m.get(), j);
+			m->f32 = requested_precision == NEUS_PRECISION_FP32;
+			if (m->f32) m->grad_fp16 = false;
+			nd_setup_module(m.get(), j, n_input_dims, gc, batch_capacity);
+			m->n_out = m->n_out_nd();
+			m->capacity = batch_capacity;
+			m->gtmp.alloc(m->n_params());
+			m->hyper = "{" + nd_hyper_members(m.get()) + ", \"output_layout\": \"" + (m->layout == ENC_LAYOUT_SOA ? "SoA" : "AoS") +
+			           "\", \"gradient_precision\": \"" + (m->grad_fp16 ? "fp16" : "fp32") + "\", \"precision\": \"" + (m->f32 ? "fp32" : "fp16") + "\"}";
+			HIP_CHECK(hipStreamSynchronize(m->core.stream));
+			*out = m.release();
+			return;
+		}
 		int dev = 0;
 		HIP_CHECK(hipGetDevice(&dev));
 		auto m = std::make_unique<NeusModule>(dev);
@@ -3608,12 +3692,46 @@ int neus_module_create_network_with_input_encoding(uint32_t n_input_dims, uint32
 			*out = m;
 			return;
 		}
-		if (ot != "HashGrid" && ot != "Grid")
+		if (!grid_otype(ot))
 			throw std::runtime_error("network with input encoding: the encoding must be Identity, Frequency, SphericalHarmonics, Composite or "
-			                         "HashGrid on gfx950");
-		if (n_input_dims != 3) throw std::runtime_error("network with input encoding: a HashGrid encodes 3 input dims");
+			                         "a grid (HashGrid / Grid / DenseGrid / TiledGrid) on gfx950");
+		const GridChoice gc = grid_choice(je, n_input_dims);
 		int dev = 0;
 		HIP_CHECK(hipGetDevice(&dev));
+		if (gc.general) {
+			// the general grid in front of a FullyFusedMLP (NdGridMlp): params [network | grid], the fused k_dnet route is not taken
+			auto m = std::make_unique<NeusModule>(dev);
+			m->kind = NeusModule::NdGridMlp;
+			module_options(m.get(), jn);
+			m->layout = ENC_LAYOUT_AOS;
+			{
+				JsonValue none; none.kind = JsonValue::Object;
+				const NeusNetworkConfig c = module_config(je, none, none, batch_capacity, true);
+				if ((uint64_t)c.n_levels * c.n_features_per_level > 128)
+					throw std::runtime_error("network with input encoding: the grid's encoded width n_features_per_level * n_levels = " +
+					                         std::to_string((uint64_t)c.n_levels * c.n_features_per_level) +
+					                         " exceeds the 128 input dims of the FullyFusedMLP on gfx950");
+			}
+			nd_setup_module(m.get(), je, n_input_dims, gc, batch_capacity);
+			const uint32_t width = m->n_out_nd();
+			const FfNet f = ff_from_json(jn, width, n_output_dims);
+			m->ff = f;
+			m->n_out = f.out_pad;
+			m->capacity = batch_capacity;
+			m->gtmp.alloc(m->n_params());
+			m->ff_acts.alloc(f.acts_halves(batch_capacity));
+			m->ff_front.alloc((size_t)batch_capacity * (f.in_pad + (size_t)f.N * f.W));
+			const uint32_t dmax = std::max(std::max(f.W, f.out_pad), f.in_pad);
+			m->ff_d[0].alloc((size_t)batch_capacity * dmax); m->ff_d[1].alloc((size_t)batch_capacity * dmax);
+			m->ff_partial.alloc((size_t)ff_wgrad_blocks(batch_capacity) * f.P);
+			m->ff_dummy.alloc(4);
+			m->hyper = "{\"otype\": \"NetworkWithInputEncoding\", \"encoding\": {" + nd_hyper_members(m.get()) + "}, \"network\": " + ff_hyper(f) +
+			           ", \"n_input_dims\": " + std::to_string(n_input_dims) + ", \"n_output_dims\": " + std::to_string(n_output_dims) +
+			           ", \"gradient_precision\": \"" + (m->grad_fp16 ? "fp16" : "fp32") + "\"}";
+			HIP_CHECK(hipStreamSynchronize(m->core.stream));
+			*out = m.release();
+			return;
+		}
 		auto m = std::make_unique<NeusModule>(dev);
 		module_options(m.get(), jn);
 		m->layout = ENC_LAYOUT_AOS;
@@ -3822,7 +3940,7 @@ int neus_module_info(const NeusModule* m, NeusModuleInfo* o) {
 		if (m->kind == NeusModule::Mlp || m->kind == NeusModule::EncMlp || m->kind == NeusModule::PfEncoding) {  // no encoding parameters
 			o->n_levels = 0; o->grid_offset = (uint32_t)m->n_params();
 		}
-		if (m->kind == NeusModule::GridMlp) o->grid_offset = m->ff.P;
+		if (m->kind == NeusModule::GridMlp || m->kind == NeusModule::NdGridMlp) o->grid_offset = m->ff.P;
 		o->per_level_scale = m->core.cfg.per_level_scale;
 	});
 }
@@ -3862,7 +3980,7 @@ int neus_module_initialize_params(NeusModule* m, uint64_t seed, float* params_fu
 			h.assign(m->n_params(), 0.f);
 			pcg32 rnd = make_pcg32(seed);
 			size_t off = 0;
-			if (m->kind == NeusModule::GridMlp) {  // NetworkWithInputEncoding::initialize_params: the network, then the encoding
+			if (m->kind == NeusModule::GridMlp || m->kind == NeusModule::NdGridMlp) {  // NetworkWithInputEncoding::initialize_params: the network, then the encoding
 				for (uint32_t l = 0; l <= m->ff.N; ++l) {
 					const float scale = std::sqrt(6.0f / (float)(m->ff.rows[l] + m->ff.cols[l]));
 					for (uint32_t i = 0; i < m->ff.rows[l] * m->ff.cols[l]; ++i) h[off + i] = rnd.next_float() * 2.0f * scale - scale;
@@ -3917,6 +4035,23 @@ static void module_forward(NeusModule* m, hipStream_t s, uint32_t n, const float
 		if (ctx) { ctx->acts.alloc(std::max<size_t>(1, m->ff.acts_halves(n))); acts = ctx->acts.p; }
 		launch_pf_rows(s, m->pf, n, input, nullptr, acts, m->ff.in_pad);
 		ff_forward(m->ff, s, n, nullptr, params, acts, (half_t*)output);
+		HIP_CHECK(hipGetLastError());
+		return;
+	}
+	if (m->kind == NeusModule::NdGrid) {
+		if (!params) throw std::runtime_error("module: null params");
+		launch_grid_nd_forward(s, n, m->nd, m->valid(), input, params, m->f32, m->nd_view(output, n), 0);
+		HIP_CHECK(hipGetLastError());
+		return;
+	}
+	if (m->kind == NeusModule::NdGridMlp) {
+		// the general grid straight into the FullyFusedMLP's fp16 input rows (padding columns zero, grid.h:1540-1550), then the layers
+		if (!params) throw std::runtime_error("module: null params");
+		const FfNet& f = m->ff;
+		half_t* acts = m->ff_acts.p;
+		if (ctx) { ctx->acts.alloc(std::max<size_t>(1, f.acts_halves(n))); acts = ctx->acts.p; }
+		launch_grid_nd_forward(s, n, m->nd, m->valid(), input, (const half_t*)params + f.P, false, m->nd_rows(acts), f.in_pad - m->n_out_nd());
+		ff_forward(f, s, n, nullptr, params, acts, (half_t*)output);
 		HIP_CHECK(hipGetLastError());
 		return;
 	}
@@ -4069,6 +4204,37 @@ int neus_module_backward(NeusModule* m, void* stream, const NeusContext* ctx, ui
 			return;
 		}
 		const uint32_t valid = m->valid();
+		if (m->kind == NeusModule::NdGrid) {
+			// kernel_grid_backward by fp32 atomics into a zeroed buffer; dL_dinput with the Jacobian gathered again from the input
+			if (dL_dinput && !params) throw std::runtime_error("module: null params");
+			if (g) {
+				HIP_CHECK(hipMemsetAsync(g, 0, (size_t)m->n_params() * 4, s));
+				launch_grid_nd_backward(s, n, m->nd, valid, input, m->nd_view(dL_doutput, n), g);
+			}
+			if (dL_dinput) launch_grid_nd_input_grad(s, n, m->nd, valid, input, params, m->f32, m->nd_view(dL_doutput, n), m->nd_scratch(), dL_dinput);
+			if (g) m->finish_grad(dL_dparams, gradient_mode, s);
+			HIP_CHECK(hipGetLastError());
+			return;
+		}
+		if (m->kind == NeusModule::NdGridMlp) {
+			// NetworkWithInputEncoding::backward (network_with_input_encoding.h:126-156): the FullyFusedMLP's backward (weight
+			// gradients, dL/dX0 as fp16 rows), then the grid's two gradients of it
+			const FfNet& f = m->ff;
+			if (!params) throw std::runtime_error("module: null params");
+			if (!ctx->acts.p) throw std::runtime_error("module backward: the context is not from this module's forward");
+			if (f.out_act != FF_NONE && !output) throw std::runtime_error("FullyFusedMLP backward: the forward output is needed for its output activation");
+			const half_t* dX0 = ff_backward_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, (const half_t*)output, g != nullptr);
+			if (g) {
+				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
+				HIP_CHECK(hipMemsetAsync(g + f.P, 0, (size_t)(m->n_params() - f.P) * 4, s));
+				launch_grid_nd_backward(s, n, m->nd, valid, input, m->nd_rows(dX0), g + f.P);
+			}
+			if (dL_dinput)
+				launch_grid_nd_input_grad(s, n, m->nd, valid, input, (const half_t*)params + f.P, false, m->nd_rows(dX0), m->nd_scratch(), dL_dinput);
+			if (g) m->finish_grad(dL_dparams, gradient_mode, s);
+			HIP_CHECK(hipGetLastError());
+			return;
+		}
 		if (m->kind == NeusModule::GridMlp) {
 			// NetworkWithInputEncoding::backward (network_with_input_encoding.h:126-156): the FullyFusedMLP's backward (weight
 			// gradients, dL/d(its input) in fp16) and the HashGrid's backward of that (grid gradients, dL_dinput from dy/dx)
@@ -4221,6 +4387,52 @@ int neus_module_backward_backward_input(NeusModule* m, void* stream, const NeusC
 				launch_pf_rows(s, m->pf, n, input, dL_ddLdinput, m->ff_front.p, f.in_pad);
 				ff_bbi_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, g != nullptr, (half_t*)dL_ddLdoutput);
 			}
+			if (g) {
+				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
+				m->finish_grad(dL_dparams, gradient_mode, s);
+			}
+			HIP_CHECK(hipGetLastError());
+			return;
+		}
+		if (m->kind == NeusModule::NdGrid) {
+			// GridEncoding::backward_backward_input (grid.h:880-1181) in one launch: the second-order dL_dparams (atomics into a zeroed
+			// buffer), dL_ddLdoutput = J u and dL_dinput (mixed terms, and the diagonal ones with Smoothstep)
+			if (!ctx || ctx->n != n) throw std::runtime_error("backward_backward_input: needs the forward's context");
+			if (!input || !dL_ddLdinput || !dL_doutput || !params) throw std::runtime_error("backward_backward_input: null input");
+			m->check_n(n, true);
+			HIP_CHECK(hipSetDevice(m->core.device));
+			StreamSwap sw(m->core, stream);
+			hipStream_t s = m->core.stream;
+			float* g = m->grad_target(dL_dparams, gradient_mode);
+			if (!g && !dL_ddLdoutput && !dL_dinput) return;
+			if (g) HIP_CHECK(hipMemsetAsync(g, 0, (size_t)m->n_params() * 4, s));
+			launch_grid_nd_bbi(s, n, m->nd, m->valid(), input, params, m->f32, dL_ddLdinput, m->nd_view(dL_doutput, n), g, m->nd_view(dL_ddLdoutput, n), 0,
+			                   dL_dinput ? m->nd_scratch() : nullptr, dL_dinput);
+			if (g) m->finish_grad(dL_dparams, gradient_mode, s);
+			HIP_CHECK(hipGetLastError());
+			return;
+		}
+		if (m->kind == NeusModule::NdGridMlp) {
+			// NetworkWithInputEncoding::backward_backward_input in the three steps of the GridMlp branch below: (1) the network's
+			// backward gives dL/dX0; (2) the grid's backward_backward_input with it as dL_doutput: the second-order grid gradient,
+			// J_enc u into the front rows, dL_dinput; (3) the FullyFusedMLP's backward_backward_input on that front
+			if (!ctx || ctx->n != n || !ctx->acts.p) throw std::runtime_error("backward_backward_input: needs the forward's context");
+			if (!input || !dL_ddLdinput || !dL_doutput || !params) throw std::runtime_error("backward_backward_input: null input");
+			m->check_n(n, true);
+			m->check_bbi_exact(dL_ddLdoutput, dL_dinput);
+			HIP_CHECK(hipSetDevice(m->core.device));
+			StreamSwap sw(m->core, stream);
+			hipStream_t s = m->core.stream;
+			float* g = m->grad_target(dL_dparams, gradient_mode);
+			if (!g && !dL_ddLdoutput && !dL_dinput) return;
+			const FfNet& f = m->ff;
+			const half_t* dX0 = nullptr;
+			if (g || dL_dinput) dX0 = ff_backward_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, nullptr, false);
+			const bool front = g || dL_ddLdoutput;
+			if (g) HIP_CHECK(hipMemsetAsync(g + f.P, 0, (size_t)(m->n_params() - f.P) * 4, s));
+			launch_grid_nd_bbi(s, n, m->nd, m->valid(), input, (const half_t*)params + f.P, false, dL_ddLdinput, m->nd_rows(dX0), g ? g + f.P : nullptr,
+			                   m->nd_rows(front ? m->ff_front.p : nullptr), f.in_pad - m->n_out_nd(), dL_dinput ? m->nd_scratch() : nullptr, dL_dinput);
+			if (front) ff_bbi_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, g != nullptr, (half_t*)dL_ddLdoutput);
 			if (g) {
 				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
 				m->finish_grad(dL_dparams, gradient_mode, s);

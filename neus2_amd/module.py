@@ -52,7 +52,9 @@ class Module:
     (default: the column-major view cpp::Module gives its caller, cpp_api.cu:58-70), "SoA" [2L, n] (GridEncoding's
     preferred layout, grid.h:2357-2359) or "paired" [L, n, 2] (this build's kernels)), or a parameter-free encoding
     (Identity, Frequency, SphericalHarmonics, Composite: input [n, n_input_dims] f32, output "AoS" [n, w] or "SoA" [w, n],
-    unpadded, n_params 0: `params` and `dL_dparams` may be empty tensors or None). dL_dparams is fp16 (tcnn's param
+    unpadded, n_params 0: `params` and `dL_dparams` may be empty tensors or None). A grid that is not the 3-dim, 2-feature,
+    hashed, linear one (2 - 4 dims, 1 / 2 / 4 / 8 features, "type" Dense / Tiled, "interpolation" Smoothstep, or "implementation":
+    "general") is the general grid: input [n, n_input_dims] f32, output "AoS" [n, F L] or "SoA" [F L, n], any n. dL_dparams is fp16 (tcnn's param
     precision) unless the config says "gradient_precision": "fp32"."""
 
     def __init__(self, handle, kind):
@@ -87,7 +89,8 @@ class Module:
 
     @classmethod
     def create_network_with_input_encoding(cls, n_input_dims, n_output_dims, encoding, network, batch_capacity=1 << 18):
-        """tcnn create_network_with_input_encoding (cpp_api.h:108; network_with_input_encoding.h): `encoding` HashGrid,
+        """tcnn create_network_with_input_encoding (cpp_api.h:108; network_with_input_encoding.h): `encoding` HashGrid (or any
+        grid create_encoding accepts, n_input_dims 2 - 4, encoded width F L <= 128, zero-padded to 16),
         Identity ({"scale", "offset"}, identity.h), Frequency ({"n_frequencies": 1..16}), SphericalHarmonics ({"degree": 1..8},
         3 dims) or Composite ({"nested": [{"n_dims_to_encode", ...}, ...]} of the last three; encoded width <= 128, padded to
         16 with ones), `network` a FullyFusedMLP of any depth / width (16..128) / activation.
@@ -110,7 +113,10 @@ class Module:
         """tcnn create_encoding(n_input_dims, encoding, requested_precision) (cpp_api.h:110; cpp_api.cu:174-180): Fp16 =
         GridEncoding<__half> (fp16 params / output), Fp32 = GridEncoding<float> (f32 params, output and gradients).
         `encoding` may also be Identity, Frequency, SphericalHarmonics or a Composite of them, on any n_input_dims and any
-        n >= 1: no parameters, output and dL_doutput in the requested precision, "output_layout" AoS or SoA."""
+        n >= 1: no parameters, output and dL_doutput in the requested precision, "output_layout" AoS or SoA.
+        Grids: otype HashGrid / Grid ("type": "Hash" | "Dense" | "Tiled") or DenseGrid / TiledGrid, n_input_dims 2 - 4,
+        n_features_per_level 1 / 2 / 4 / 8, "interpolation": "Linear" | "Smoothstep"; "implementation": "general" puts the 3-dim,
+        2-feature, hashed, linear config on the general kernels too."""
         text = encoding if isinstance(encoding, str) else json.dumps(encoding)
         h = C.c_void_p()
         check(lib().neus_module_create_encoding(C.c_uint32(n_input_dims), text.encode(), C.c_int(int(Precision(requested_precision))),
@@ -172,7 +178,8 @@ class Module:
         if L == 0:  # a parameter-free encoding: unpadded width
             w = self.n_output_dims
             return {"AoS": (n, w), "SoA": (w, n)}[self.output_layout]
-        return {"AoS": (n, 2 * L), "SoA": (2 * L, n), "paired": (L, n, 2)}[self.output_layout]
+        w = self.n_output_dims  # F L: 2 L for the 3-D, 2-feature grid
+        return {"AoS": (n, w), "SoA": (w, n), "paired": (L, n, 2)}[self.output_layout]
 
     def gradient_buffer(self):
         """A zeroed dL_dparams tensor of the module's gradient precision."""

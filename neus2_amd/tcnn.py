@@ -11,8 +11,10 @@ double backward is provided for hidden activation ReLU / None with a linear outp
 a SphericalHarmonics segment (no second derivative of it is implemented); a cotangent for the parameter gradient (a
 gradient of a gradient in the parameters) is not supported.
 
-Encodings: HashGrid, and the parameter-free Identity, Frequency, SphericalHarmonics and Composite (of those three), whose
-`params` is an empty Parameter.
+Encodings: grids (HashGrid / Grid / DenseGrid / TiledGrid: 2, 3 or 4 input dims, 1, 2, 4 or 8 features per level, "type" Hash /
+Dense / Tiled, "interpolation" Linear / Smoothstep; with Smoothstep the double backward carries the grid's diagonal second
+derivatives), and the parameter-free Identity, Frequency, SphericalHarmonics and Composite (of those three), whose `params`
+is an empty Parameter.
 
 Two autograd Functions talk to a small backend object (`NativeBackend` over module.Module by default):
     n_params, n_input_dims, n_output_dims (the backend's, possibly padded, output width), param_dtype, output_dtype,
@@ -211,7 +213,7 @@ def _text(cfg):
 
 
 class Encoding(Module):
-    """Encoding(n_input_dims, encoding_config, seed=1337, dtype=None): the HashGrid, or a parameter-free Identity /
+    """Encoding(n_input_dims, encoding_config, seed=1337, dtype=None): a grid (2 - 4 input dims), or a parameter-free Identity /
     Frequency / SphericalHarmonics / Composite encoding (`params` is then empty). dtype None / torch.float16: fp16 table
     and output (loss_scale 128); torch.float32: the fp32 encoding (loss_scale 1)."""
 
@@ -246,7 +248,7 @@ class Network(Module):
 
 
 class NetworkWithInputEncoding(Module):
-    """NetworkWithInputEncoding(n_input_dims, n_output_dims, encoding_config, network_config, seed=1337): a HashGrid,
+    """NetworkWithInputEncoding(n_input_dims, n_output_dims, encoding_config, network_config, seed=1337): a grid (2 - 4 dims),
     Identity, Frequency, SphericalHarmonics or Composite encoding in front of a FullyFusedMLP, as one module with
     parameters [network | grid] (the network alone for the parameter-free encodings)."""
 
