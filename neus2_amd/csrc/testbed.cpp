@@ -3186,13 +3186,23 @@ int neus_mfma_probe(const uint16_t* A, const uint16_t* B, float* C) {
 } // extern "C"
 
 // ============================================================ tcnn-shaped operator modules (cpp_api.h:66-110)
-// A module owns a private NeusTestbed core holding only the network half (setup_network): grid tables, parameter
-// layout, the fp16 / transposed weight copies the kernels read and one batch of forward / backward workspace. The
-// parameters come in through the explicit `params` pointer of every call (copied into the core's fp16 buffer and
-// re-prepared), as tcnn::cpp::Module does; gradients leave through dL_dparams with EGradientMode semantics
-// (object.h:90-94). Kinds: the NeuS NerfNetwork (nerf_network.h: encoding + density MLP + rgb MLP + variance,
-// input NerfCoordinate [n][7] f32, output [n][16] fp16) and the HashGrid encoding (grid.h, input [n][3] f32, output
-// [L][n] half2 = features 2l, 2l+1 of level l adjacent).
+// A module is tcnn's NetworkWithInputEncoding = encoding x network, held as two parts, with the call protocol (checks,
+// stream, gradient modes) written once in each neus_module_* entry point:
+//   Enc    the encoding part: Identity (the MLP's own input stage, ffmlp.hip), a parameter-free encoding (Identity,
+//          Frequency, SphericalHarmonics or a Composite of them, encodings.hip), the 3-D 2-feature HashGrid in fp16
+//          (grid.hip's paired-layout kernels; its context keeps dy/dx) or in fp32 (grid_f32.hip, stand-alone only), or
+//          the general grid (grid_nd.hip). encode / backward / backward_backward are one switch each and read or write
+//          either a caller tensor (stand-alone encoding: AoS / SoA / paired) or the MLP's fp16 rows [n][in_pad] (EncIO).
+//   FfNet  the network part: none, or a FullyFusedMLP (ffmlp.hip) with its workspace FfWork.
+// The parameters are [network | encoding] and come in through the explicit `params` pointer of every call, as
+// tcnn::cpp::Module does; gradients leave through dL_dparams with EGradientMode semantics (object.h:90-94).
+// Two fused specials are explicit cases beside the composed path (NeusModule::Fused): the NeuS NerfNetwork
+// (nerf_network.h: encoding + density MLP + rgb MLP + variance, input NerfCoordinate [n][7] f32, output [n][16] fp16),
+// which delegates to the core's net_forward / net_backward, and HashGrid -> one hidden ReLU layer -> <= 16 linear
+// outputs on the fused k_dnet kernel (mlp.hip), which shares the HashGrid variant's encode / scatter / ddx steps.
+// A module owns a private NeusTestbed core and touches it only through: setup_network, net_forward, net_backward,
+// prepare_weights, initial_params_rng, valid_level_at, gl, lay, cfg, swork, scan_tmp (+ scan_tmp_bytes), params_h, tbuf,
+// device, stream.
 namespace {
 
 std::string fmt_float(float v) { char b[32]; std::snprintf(b, sizeof(b), "%.9g", (double)v); return b; }
@@ -3231,15 +3241,17 @@ struct StreamSwap {  // run a call's launches on the caller's stream (NULL: the 
 
 struct NeusContext {
 	uint32_t n = 0;
-	Dev<float> dydx;     // encoding: dy/dx [6L][n] of the forward (prepare_input_gradients)
-	Dev<uint32_t> enc;   // network with input encoding: the forward's paired encoding [L][n] (the MLP input)
+	Dev<float> dydx;     // HashGrid: dy/dx [6L][n] of the forward (prepare_input_gradients)
+	Dev<uint32_t> enc;   // HashGrid in front of a network: the forward's paired encoding [L][n] (k_dnet's input)
 	Dev<half_t> acts;    // FullyFusedMLP: the forward's input X0 [n][in_pad] and hidden outputs [N][n][W] (post-activation)
 };
 
-// tcnn FullyFusedMLP shape (fully_fused_mlp.cu:816-879): weight matrices [W][in_pad], (N - 1) x [W][W], [out_pad][W]
+namespace {
+
+// ---------------------------------------------------------------- the network part
+// tcnn FullyFusedMLP shape (fully_fused_mlp.cu:816-879): weight matrices [W][in_pad], (N - 1) x [W][W], [out_pad][W]; P = 0: no network
 struct FfNet {
 	uint32_t W = 0, N = 0, n_in = 0, in_pad = 0, n_out = 0, out_pad = 0, act = FF_RELU, out_act = FF_NONE;
-	float in_scale = 1.f, in_offset = 0.f;  // the Identity encoding's scale / offset (identity.h:44-70)
 	std::vector<uint32_t> off, rows, cols;
 	uint32_t P = 0;
 	void build() {
@@ -3261,190 +3273,159 @@ struct FfNet {
 		                         "Softplus; Sine has no backward in tcnn's fully fused MLP)");
 	}
 };
-
-struct NeusModule {
-	// Network: the NeuS NerfNetwork; Encoding: a HashGrid; DensityNet: tcnn's NetworkWithInputEncoding(HashGrid ->
-	// FullyFusedMLP with 1 hidden ReLU layer -> 16 linear outputs), the network whose backward_backward_input tcnn
-	// implements (network_with_input_encoding.h:159-250, fully_fused_mlp.cu:1088-1198)
-	// Mlp: tcnn::cpp::create_network = NetworkWithInputEncoding(Identity -> FullyFusedMLP) (cpp_api.cu:170-172), ffmlp.hip
-	// GridMlp: NetworkWithInputEncoding(HashGrid -> any FullyFusedMLP), composed of the encoding kernels and ffmlp.hip's layers
-	// PfEncoding: a parameter-free encoding (Identity, Frequency, SphericalHarmonics or a Composite of them), encodings.hip
-	// EncMlp: NetworkWithInputEncoding(such an encoding -> any FullyFusedMLP): encodings.hip writes the MLP's input rows
-	// NdGrid: the general grid encoding (grid_nd.hip: 2..4 dims, 1 / 2 / 4 / 8 features, Hash / Dense / Tiled, Linear / Smoothstep)
-	// NdGridMlp: NetworkWithInputEncoding(such a grid -> any FullyFusedMLP): grid_nd.hip writes the MLP's input rows
-	enum Kind { Network = 0, Encoding = 1, DensityNet = 2, Mlp = 3, GridMlp = 4, PfEncoding = 5, EncMlp = 6, NdGrid = 7, NdGridMlp = 8 } kind;
-	FfNet ff;
-	GridNd nd{};                             // NdGrid, NdGridMlp: the level tables
-	Dev<float> nd_partial;                   // NdGrid, NdGridMlp: dL_dinput's per-level terms [D L][capacity] (first use)
-	PfEnc pf{};                              // PfEncoding, EncMlp: the segments
-	Dev<half_t> ff_acts, ff_front, ff_d[2];  // Mlp: inference activations, backward-backward fronts, delta ping-pong
-	Dev<float> ff_partial, ff_dummy;         // Mlp: per-block weight-gradient rows
-	uint32_t n_mlp = 0, dn_width = 0, dn_de = 0;  // DensityNet: MLP parameters W DE + 16 W ahead of the grid, width, padded input
-	Dev<uint32_t> u_tmp;                          // DensityNet: dy/dx . dL_ddLdinput, paired
-	Dev<float> dn_partial, dn_dummy;              // DensityNet: per-block weight-gradient rows
-	NeusTestbed core;
-	uint32_t capacity = 0, n_in = 0, n_out = 0;
-	int training_step = 0;              // GridEncoding::set_training_step (grid.h:2427-2437): 0 = every level
-	uint32_t indeed_batch = 0;          // NeuS backward normalisation of the eikonal entries; 0 = the call's n
-	std::string hyper;
-	// encoding output layout (ENC_LAYOUT_*): AoS [n][2L] = the column-major matrix tcnn's cpp::Module wraps around the
-	// caller's buffer (cpp_api.cu:58-70); SoA [2L][n] = GridEncoding::preferred_output_layout (grid.h:2357-2359);
-	// paired [L][n] half2 = this build's kernels
-	uint32_t layout = ENC_LAYOUT_AOS;
-	bool grad_fp16 = true;              // dL_dparams in param precision (fp16, trainer.h:72-109) or fp32
-	bool f32 = false;                   // Encoding created with requested_precision fp32: float params / output / gradients
-	Dev<uint32_t> enc_tmp, denc_tmp;    // paired-layout staging of non-paired module I/O
-	Dev<float> gtmp;                    // gradients of an Accumulate call (and of every fp16-gradient call)
-	Dev<float> ddx_partial;             // backward_backward_input's dL_dinput: per-level terms [3 L][capacity] (first use)
-	Dev<float4> dpos, v4;
-	Dev<half_t> zero_h;
-	Dev<float4> zero_v;
-	explicit NeusModule(int device) : core(device) {}
-	uint64_t n_params() const {
-		if (kind == Mlp || kind == EncMlp) return ff.P;
-		if (kind == PfEncoding) return 0;
-		if (kind == GridMlp) return ff.P + core.lay.n_grid;
-		if (kind == NdGrid || kind == NdGridMlp) return (kind == NdGridMlp ? ff.P : 0) + (uint64_t)nd.gl.offset[nd.gl.n_levels] * nd.F;
-		return kind == Network ? core.lay.P : (kind == DensityNet ? n_mlp + core.lay.n_grid : core.lay.n_grid);
-	}
-	uint32_t valid() const { return core.valid_level_at(training_step); }
-	void load_params(const void* params, hipStream_t s) {
-		if (!params) throw std::runtime_error("module: null params");
-		if (kind == Network) {
-			HIP_CHECK(hipMemcpyAsync(core.params_h.p, params, (size_t)core.lay.P * 2, hipMemcpyDeviceToDevice, s));
-			core.prepare_weights();
-		} else {
-			HIP_CHECK(hipMemcpyAsync(core.params_h.p + core.lay.grid_off, params, (size_t)core.lay.n_grid * 2, hipMemcpyDeviceToDevice, s));
-		}
-	}
-	void check_n(uint32_t n, bool backward) const {
-		if (n > capacity) throw std::runtime_error("module: n_elements exceeds the module's batch capacity");
-		if (backward && kind == Network && (n == 0 || n % 128 != 0))
-			throw std::runtime_error("module backward: n_elements must be a positive multiple of 128 (fully_fused_mlp.cu:779-781)");
-		if ((kind == Mlp || kind == GridMlp || kind == EncMlp || kind == NdGridMlp) && n % 128 != 0) throw std::runtime_error("FullyFusedMLP: batch size must be a multiple of 128 (fully_fused_mlp.cu:779-781)");
-	}
-	// the destination of this call's parameter gradients (Overwrite: dL_dparams itself; Accumulate: a scratch buffer)
-	float* grad_target(void* dL_dparams, int mode) {
-		if (mode == NEUS_GRADIENT_IGNORE) return nullptr;
-		if (!dL_dparams) throw std::runtime_error("module: dL_dparams is null with a gradient mode other than Ignore");
-		if (mode != NEUS_GRADIENT_OVERWRITE && mode != NEUS_GRADIENT_ACCUMULATE) throw std::runtime_error("module: unknown gradient mode");
-		if (mode == NEUS_GRADIENT_OVERWRITE && !grad_fp16) return (float*)dL_dparams;
-		return gtmp.p;
-	}
-	void finish_grad(void* dL_dparams, int mode, hipStream_t s) {
-		if (grad_fp16) launch_grad_to_half(s, (uint32_t)n_params(), gtmp.p, (half_t*)dL_dparams, mode == NEUS_GRADIENT_ACCUMULATE);
-		else if (mode == NEUS_GRADIENT_ACCUMULATE) launch_add_f32(s, (uint32_t)n_params(), gtmp.p, (float*)dL_dparams);
-	}
-	bool pf_has_sh() const {
-		for (uint32_t q = 0; q < pf.n_seg; ++q) if (pf.seg[q].type == PF_SH) return true;
-		return false;
-	}
-	// a caller tensor of the stand-alone parameter-free encoding (output, dL_doutput, dL_ddLdoutput): unpadded AoS / SoA
-	PfView pf_view(const void* p, uint32_t n) const {
-		return layout == ENC_LAYOUT_SOA ? PfView{const_cast<void*>(p), 1, n, f32 ? 1u : 0u} : PfView{const_cast<void*>(p), pf.width, 1, f32 ? 1u : 0u};
-	}
-	// backward_backward_input's dL_dinput needs the encoding's second derivative: none is implemented for the spherical
-	// harmonics (nor has tcnn's SphericalHarmonicsEncoding a backward_backward_input)
-	void check_bbi_sh(const float* dL_dinput) const {
-		if (dL_dinput && pf_has_sh())
-			throw std::runtime_error("backward_backward_input: dL_dinput is not supported with a SphericalHarmonics segment (the second "
-			                         "derivative of the spherical harmonics is not implemented); dL_ddLdoutput and the parameter gradients are");
-	}
-	// a caller tensor of the stand-alone general grid (output, dL_doutput, dL_ddLdoutput): AoS [n][F L] or SoA [F L][n]
-	PfView nd_view(const void* p, uint32_t n) const {
-		return layout == ENC_LAYOUT_SOA ? PfView{const_cast<void*>(p), 1, n, f32 ? 1u : 0u} : PfView{const_cast<void*>(p), n_out_nd(), 1, f32 ? 1u : 0u};
-	}
-	uint32_t n_out_nd() const { return nd.F * nd.gl.n_levels; }
-	// the MLP's fp16 rows [n][in_pad] as the general grid's tensor (features in columns [0, F L))
-	PfView nd_rows(const half_t* rows) const { return PfView{const_cast<half_t*>(rows), ff.in_pad, 1, 0u}; }
-	float* nd_scratch() { nd_partial.alloc((size_t)nd.D * nd.gl.n_levels * capacity); return nd_partial.p; }
-	float* ddx_scratch() { ddx_partial.alloc((size_t)3 * core.lay.L * capacity); return ddx_partial.p; }
-	// backward_backward_input's dL_ddLdoutput / dL_dinput of a network: the fronts / backs chain has no act'' term, so they
-	// are exact only where act'' = 0 (hidden ReLU or None) and the output is linear
-	void check_bbi_exact(const void* dL_ddLdoutput, const float* dL_dinput) const {
-		if (!dL_ddLdoutput && !dL_dinput) return;
-		if (kind == DensityNet || ((ff.act == FF_RELU || ff.act == FF_NONE) && ff.out_act == FF_NONE)) return;
-		throw std::runtime_error("backward_backward_input: dL_ddLdoutput and dL_dinput are exact only for hidden activation ReLU or None with "
-		                         "output activation None (the second derivative of any other activation is not implemented); pass null "
-		                         "for both to get the parameter gradients alone");
-	}
-	// a caller-layout encoding tensor (dL_doutput) as the kernels' paired layout
-	const half_t* paired_in(const void* x, uint32_t n, hipStream_t s) {
-		if (layout == ENC_LAYOUT_PAIRED) return (const half_t*)x;
-		launch_enc_from_layout(s, n, core.lay.L, (const half_t*)x, layout, denc_tmp.p);
-		return (const half_t*)denc_tmp.p;
+// A FullyFusedMLP from its config (fully_fused_mlp.cu:816-879): n_neurons 16 / 32 / 64 / 128, n_hidden_layers >= 1, input and
+// output padded to multiples of 16 (cpp::Module::n_output_dims = the padded output width). Host only.
+FfNet ff_from_json(const JsonValue& j, uint32_t n_input_dims, uint32_t n_output_dims) {
+	const std::string ot = j.string("otype", "FullyFusedMLP");
+	if (ot != "FullyFusedMLP" && ot != "MegakernelMLP" && ot != "CutlassMLP")
+		throw std::runtime_error("only FullyFusedMLP networks are implemented on gfx950");
+	FfNet f;
+	f.W = (uint32_t)j.number("n_neurons", 64);
+	if (f.W != 16 && f.W != 32 && f.W != 64 && f.W != 128)
+		throw std::runtime_error("FullyFusedMLP only supports 16, 32, 64, and 128 neurons, but got " + std::to_string(f.W));
+	const double nh = j.number("n_hidden_layers", 1);
+	if (nh < 1 || nh > 32) throw std::runtime_error("FullyFusedMLP requires at least 1 hidden layer (3 layers in total).");
+	f.N = (uint32_t)nh;
+	if (n_input_dims == 0 || n_input_dims > 128) throw std::runtime_error("FullyFusedMLP: 1..128 input dims on gfx950");
+	if (n_output_dims == 0 || n_output_dims > 128) throw std::runtime_error("FullyFusedMLP: 1..128 output dims on gfx950");
+	f.n_in = n_input_dims; f.in_pad = (n_input_dims + 15) / 16 * 16;
+	f.n_out = n_output_dims; f.out_pad = (n_output_dims + 15) / 16 * 16;
+	f.act = FfNet::activation(j.string("activation", "ReLU"));
+	f.out_act = FfNet::activation(j.string("output_activation", "None"));
+	f.build();
+	return f;
+}
+std::string ff_hyper(const FfNet& f) {
+	static const char* an[6] = {"None", "ReLU", "Exponential", "Sigmoid", "Squareplus", "Softplus"};
+	return "{\"otype\": \"FullyFusedMLP\", \"n_neurons\": " + std::to_string(f.W) + ", \"n_hidden_layers\": " + std::to_string(f.N) +
+	       ", \"activation\": \"" + an[f.act] + "\", \"output_activation\": \"" + an[f.out_act] + "\"}";
+}
+// the network's workspace for one batch of `capacity` samples: inference activations, backward-backward fronts, the delta
+// ping-pong and the per-block weight-gradient rows
+struct FfWork {
+	Dev<half_t> acts, front, d[2];
+	Dev<float> partial, dummy;
+	void alloc(const FfNet& f, uint32_t capacity) {
+		acts.alloc(f.acts_halves(capacity));
+		front.alloc((size_t)capacity * (f.in_pad + (size_t)f.N * f.W));
+		const uint32_t dmax = std::max(std::max(f.W, f.out_pad), f.in_pad);
+		d[0].alloc((size_t)capacity * dmax); d[1].alloc((size_t)capacity * dmax);
+		partial.alloc((size_t)ff_wgrad_blocks(capacity) * f.P);
+		dummy.alloc(4);
 	}
 };
+// where the backward's layer 0 puts dL/d(network input): fp16 rows [n][in_pad] for the encoding's backward, or, behind the
+// Identity encoding (`direct`), W_0^T D_0 x scale straight into the caller's fp32 dL_dinput [n][n_in] (null: not computed)
+struct FfSink { bool direct; float* dL_dinput; float scale; };
 
-// module options (this build's keys, beside tcnn's): "gradient_precision": "fp16" (default, tcnn's param precision) |
-// "fp32"; encoding "output_layout": "AoS" (default: cpp::Module's column-major view) | "SoA" | "paired"
-static void module_options(NeusModule* m, const JsonValue& j) {
-	const std::string gp = j.string("gradient_precision", "fp16");
-	if (gp != "fp16" && gp != "fp32") throw std::runtime_error("module: gradient_precision must be fp16 or fp32");
-	m->grad_fp16 = gp == "fp16";
-	const std::string ol = j.string("output_layout", "AoS");
-	if (ol == "AoS") m->layout = ENC_LAYOUT_AOS;
-	else if (ol == "SoA") m->layout = ENC_LAYOUT_SOA;
-	else if (ol == "paired") m->layout = ENC_LAYOUT_PAIRED;
-	else throw std::runtime_error("encoding module: output_layout must be AoS, SoA or paired");
+// FullyFusedMLP passes (ffmlp.hip). acts: X0 [n][in_pad] then hidden l at n (in_pad + l W), each [n][W].
+const half_t* ff_mat(const FfNet& f, const void* params, uint32_t l) { return (const half_t*)params + f.off[l]; }
+half_t* ff_hidden(const FfNet& f, const half_t* acts, uint32_t n, uint32_t l) { return const_cast<half_t*>(acts) + (size_t)n * f.in_pad + (size_t)l * n * f.W; }
+FfLayer ff_layer(const half_t* W, uint32_t O, uint32_t K, bool trans, const half_t* in, uint32_t ldi, uint32_t n) {
+	FfLayer L{};
+	L.W = W; L.O = O; L.K = K; L.trans = trans ? 1u : 0u; L.in = in; L.ldi = ldi; L.n = n;
+	return L;
 }
-static void module_common_init(NeusModule* m, uint32_t capacity) {
-	m->capacity = capacity;
-	const size_t P = m->n_params();
-	m->gtmp.alloc(P);
-	m->dpos.alloc(capacity); m->v4.alloc(capacity);
-	m->zero_h.alloc((size_t)2 * m->core.lay.L * capacity); m->zero_v.alloc(capacity);
-	if ((m->kind == NeusModule::Encoding && m->layout != ENC_LAYOUT_PAIRED) || m->kind == NeusModule::DensityNet || m->kind == NeusModule::GridMlp) {
-		m->enc_tmp.alloc((size_t)m->core.lay.L * capacity); m->denc_tmp.alloc((size_t)m->core.lay.L * capacity);
+// forward (mlp_fused_forward, fully_fused_mlp.cu:678-812) on the encoded rows X0 in acts: hidden layers act(W x), output
+// out_act(W_N h)
+void ff_forward(const FfNet& f, hipStream_t s, uint32_t n, const void* params, half_t* acts, half_t* output) {
+	const half_t* x = acts;
+	uint32_t ldx = f.in_pad;
+	for (uint32_t l = 0; l <= f.N; ++l) {
+		FfLayer L = ff_layer(ff_mat(f, params, l), f.rows[l], f.cols[l], false, x, ldx, n);
+		L.mode = FF_MODE_ACT;
+		L.act = l == f.N ? f.out_act : f.act;
+		L.out = l == f.N ? output : ff_hidden(f, acts, n, l);
+		L.ldo = l == f.N ? f.out_pad : f.W;
+		launch_ff_layer(s, L);
+		x = L.out; ldx = f.W;
 	}
-	if (m->kind == NeusModule::GridMlp) {
-		const FfNet& f = m->ff;
-		m->u_tmp.alloc((size_t)m->core.lay.L * capacity);
-		m->ff_acts.alloc(f.acts_halves(capacity));
-		m->ff_front.alloc((size_t)capacity * (f.in_pad + (size_t)f.N * f.W));
-		const uint32_t dmax = std::max(std::max(f.W, f.out_pad), f.in_pad);
-		m->ff_d[0].alloc((size_t)capacity * dmax); m->ff_d[1].alloc((size_t)capacity * dmax);
-		m->ff_partial.alloc((size_t)ff_wgrad_blocks(capacity) * f.P);
-		m->ff_dummy.alloc(4);
+}
+// delta through layer l (l >= 1) to the input of layer l: act'(h_{l-1}) (W_l^T d)
+void ff_back_through(const FfNet& f, hipStream_t s, uint32_t n, const void* params, uint32_t l, const half_t* d, uint32_t ldd, const half_t* acts_fwd,
+                     half_t* out) {
+	FfLayer L = ff_layer(ff_mat(f, params, l), f.cols[l], f.rows[l], true, d, ldd, n);
+	L.mode = FF_MODE_DACT; L.act = f.act; L.out = out; L.ldo = f.W;
+	L.aux = ff_hidden(f, acts_fwd, n, l - 1); L.ldx = f.W;
+	launch_ff_layer(s, L);
+}
+void ff_wgrad(const FfNet& f, hipStream_t s, uint32_t n, uint32_t l, const half_t* d, uint32_t ldd, const half_t* x, uint32_t ldx, float* partial) {
+	FfWgrad G{};
+	G.D = d; G.ldd = ldd; G.O = f.rows[l]; G.X = x; G.ldx = ldx; G.I = f.cols[l];
+	G.partial = partial; G.ld_partial = f.P; G.off = f.off[l]; G.n = n;
+	launch_ff_wgrad(s, G);
+}
+// FullyFusedMLP::backward_impl (fully_fused_mlp.cu:967-1085): the output activation's backward on dL/doutput, the deltas
+// through the hidden layers (activation derivative from the stored outputs), with wgrad dW = D^T x per layer into the
+// partials, and layer 0 into the sink: dL/dX0 as fp16 rows (returned; the delta ping-pong buffer), or dL/dinput = W_0^T D_0
+// through the Identity encoding's backward (identity.h:86-104: x scale)
+const half_t* ff_backward_chain(const FfNet& f, FfWork& w, hipStream_t s, uint32_t n, const void* params, const half_t* acts, const half_t* dL_doutput,
+                                const half_t* output, bool wgrad, const FfSink& sink) {
+	const half_t* d = dL_doutput;
+	int pp = 0;
+	if (f.out_act != FF_NONE) { launch_ff_out_delta(s, n, f.out_pad, f.out_act, d, output, w.d[0].p); d = w.d[0].p; pp = 1; }
+	uint32_t ldd = f.out_pad;
+	for (uint32_t l = f.N + 1; l-- > 0;) {
+		const half_t* x = l == 0 ? acts : ff_hidden(f, acts, n, l - 1);
+		if (wgrad) ff_wgrad(f, s, n, l, d, ldd, x, l == 0 ? f.in_pad : f.W, w.partial.p);
+		if (l > 0) {
+			ff_back_through(f, s, n, params, l, d, ldd, acts, w.d[pp].p);
+			d = w.d[pp].p; pp ^= 1; ldd = f.W;
+		} else if (!sink.direct) {
+			FfLayer L = ff_layer(ff_mat(f, params, 0), f.in_pad, f.W, true, d, ldd, n);
+			L.mode = FF_MODE_ACT; L.act = FF_NONE; L.out = w.d[pp].p; L.ldo = f.in_pad;
+			launch_ff_layer(s, L);
+			d = w.d[pp].p;
+		} else if (sink.dL_dinput) {
+			FfLayer L = ff_layer(ff_mat(f, params, 0), f.in_pad, f.W, true, d, ldd, n);
+			L.mode = FF_MODE_F32; L.out_f = sink.dL_dinput; L.ldo = f.n_in; L.o_lim = f.n_in; L.out_scale = sink.scale;
+			launch_ff_layer(s, L);
+		}
 	}
-	if (m->kind == NeusModule::DensityNet) {
-		m->u_tmp.alloc((size_t)m->core.lay.L * capacity);
-		m->dn_partial.alloc((size_t)dnet_blocks(capacity) * m->n_mlp);
-		m->dn_dummy.alloc(4);
+	return d;
+}
+// FullyFusedMLP::backward_backward_input_impl (fully_fused_mlp.cu:1088-1198) with the front f_0 = the network's
+// dL_ddLdinput already in w.front as rows [n][in_pad]: fronts f_i = act'(h_{i-1}) (W_{i-1} f_{i-1}); dL_ddLdoutput (when
+// asked for) = the front carried through the output matrix, f_{N+1} = W_N f_N, as [n][out_pad] fp16; with wgrad the backs
+// b_{N+2} = dL_doutput, b_i = act'(h_{i-2}) (W_{i-1}^T b_{i+1}) and dW_{i-1} = b_{i+1} f_{i-1}^T into the partials
+void ff_bbi_chain(const FfNet& f, FfWork& w, hipStream_t s, uint32_t n, const void* params, const half_t* acts, const half_t* dL_doutput, bool wgrad,
+                  half_t* dL_ddLdoutput) {
+	half_t* fr = w.front.p;
+	auto front = [&](uint32_t i) { return i == 0 ? fr : fr + (size_t)n * f.in_pad + (size_t)(i - 1) * n * f.W; };
+	for (uint32_t i = 1; i <= f.N; ++i) {
+		FfLayer L = ff_layer(ff_mat(f, params, i - 1), f.rows[i - 1], f.cols[i - 1], false, front(i - 1), i == 1 ? f.in_pad : f.W, n);
+		L.mode = FF_MODE_DACT; L.act = f.act; L.out = front(i); L.ldo = f.W;
+		L.aux = ff_hidden(f, acts, n, i - 1); L.ldx = f.W;
+		launch_ff_layer(s, L);
 	}
-	HIP_CHECK(hipMemset(m->zero_h.p, 0, m->zero_h.n * sizeof(half_t)));
-	HIP_CHECK(hipMemset(m->zero_v.p, 0, m->zero_v.n * sizeof(float4)));
-	HIP_CHECK(hipStreamSynchronize(m->core.stream));
+	if (dL_ddLdoutput) {
+		FfLayer L = ff_layer(ff_mat(f, params, f.N), f.rows[f.N], f.cols[f.N], false, front(f.N), f.W, n);
+		L.mode = FF_MODE_ACT; L.act = FF_NONE; L.out = dL_ddLdoutput; L.ldo = f.out_pad;
+		launch_ff_layer(s, L);
+	}
+	if (!wgrad) return;
+	const half_t* b = dL_doutput;
+	uint32_t ldb = f.out_pad;
+	int pp = 0;
+	for (uint32_t l = f.N + 1; l-- > 0;) {
+		ff_wgrad(f, s, n, l, b, ldb, front(l), l == 0 ? f.in_pad : f.W, w.partial.p);
+		if (l > 0) {
+			ff_back_through(f, s, n, params, l, b, ldb, acts, w.d[pp].p);
+			b = w.d[pp].p; pp ^= 1; ldb = f.W;
+		}
+	}
+}
+// the weight gradients from the per-block partials (fixed order), into the head of g
+void ff_reduce(const FfNet& f, FfWork& w, hipStream_t s, uint32_t n_blocks, float* g) {
+	launch_mlp_grad_reduce(s, MlpGradReduce{w.partial.p, n_blocks, f.P, g, nullptr, nullptr, 0, w.dummy.p});
 }
 
-int neus_module_create_nerf_network(const char* config_json, uint32_t batch_capacity, NeusModule** out) {
-	return guard([&] {
-		if (!config_json || !out) throw std::runtime_error("neus_module_create_nerf_network: null argument");
-		if (batch_capacity == 0 || batch_capacity % 128 != 0 || batch_capacity > (1u << 24))
-			throw std::runtime_error("batch_capacity must be a positive multiple of 128 (<= 2^24)");
-		const JsonValue j = parse_json(config_json);
-		int dev = 0;
-		HIP_CHECK(hipGetDevice(&dev));
-		auto m = std::make_unique<NeusModule>(dev);
-		m->kind = NeusModule::Network;
-		module_options(m.get(), j);
-		m->layout = ENC_LAYOUT_AOS;
-		m->core.setup_network(module_config(j.object("encoding"), j.object("network"), j.object("rgb_network"), batch_capacity), nullptr);
-		m->n_in = COORD_W; m->n_out = OUT_W;
-		const NeusNetworkConfig& c = m->core.cfg;
-		m->hyper = "{\"otype\": \"NerfNetwork\", \"n_levels\": " + std::to_string(c.n_levels) + ", \"n_neurons\": " + std::to_string(c.n_neurons) +
-		           ", \"log2_hashmap_size\": " + std::to_string(c.log2_hashmap_size) + ", \"per_level_scale\": " + fmt_float(c.per_level_scale) +
-		           ", \"gradient_precision\": \"" + (m->grad_fp16 ? "fp16" : "fp32") + "\"}";
-		module_common_init(m.get(), batch_capacity);
-		*out = m.release();
-	});
-}
-
+// ---------------------------------------------------------------- the encoding part
 // tcnn's parameter-free encodings from their config (encoding.cu create_encoding; identity.h, frequency.h,
 // spherical_harmonics.h, composite.h): one segment, or a Composite's nested encodings over consecutive input dims (the
 // last may leave n_dims_to_encode out and takes the rest). Host only: every check runs before a device call.
-static bool pf_otype(const std::string& ot) { return ot == "Identity" || ot == "Frequency" || ot == "SphericalHarmonics" || ot == "Composite"; }
-static void pf_add_segment(PfEnc& E, const JsonValue& j, const std::string& ot, uint32_t dims) {
+bool pf_otype(const std::string& ot) { return ot == "Identity" || ot == "Frequency" || ot == "SphericalHarmonics" || ot == "Composite"; }
+void pf_add_segment(PfEnc& E, const JsonValue& j, const std::string& ot, uint32_t dims) {
 	if (E.n_seg == PF_MAX_SEGMENTS) throw std::runtime_error("Composite: at most 8 nested encodings");
 	if (dims == 0) throw std::runtime_error(ot + ": at least 1 input dim to encode");
 	PfSegment g{};
@@ -3466,7 +3447,7 @@ static void pf_add_segment(PfEnc& E, const JsonValue& j, const std::string& ot, 
 	E.seg[E.n_seg++] = g;
 	E.n_in += dims; E.width += w;
 }
-static PfEnc pf_from_json(const JsonValue& j, uint32_t n_input_dims) {
+PfEnc pf_from_json(const JsonValue& j, uint32_t n_input_dims) {
 	if (n_input_dims == 0 || n_input_dims > (1u << 16)) throw std::runtime_error("encoding module: n_input_dims must be in 1..65536");
 	PfEnc E{};
 	const std::string ot = j.string("otype", "");
@@ -3497,49 +3478,15 @@ static PfEnc pf_from_json(const JsonValue& j, uint32_t n_input_dims) {
 		                         std::to_string(n_input_dims));
 	return E;
 }
-// the accepted config back as JSON members (no braces): the otype with its own keys, nested types included
-static std::string pf_hyper_segment(const PfSegment& g) {
+std::string pf_hyper_segment(const PfSegment& g) {
 	if (g.type == PF_SH) return "\"otype\": \"SphericalHarmonics\", \"degree\": " + std::to_string(g.param);
 	if (g.type == PF_FREQUENCY) return "\"otype\": \"Frequency\", \"n_frequencies\": " + std::to_string(g.param);
 	return "\"otype\": \"Identity\", \"scale\": " + fmt_float(g.scale) + ", \"offset\": " + fmt_float(g.offset);
 }
-static std::string pf_hyper_members(const PfEnc& E, bool composite) {
-	if (!composite) return pf_hyper_segment(E.seg[0]);
-	std::string s = "\"otype\": \"Composite\", \"nested\": [";
-	for (uint32_t q = 0; q < E.n_seg; ++q)
-		s += std::string(q ? ", " : "") + "{\"n_dims_to_encode\": " + std::to_string(E.seg[q].dims) + ", " + pf_hyper_segment(E.seg[q]) + "}";
-	return s + "]";
-}
-// create_encoding with a parameter-free encoding: any n_input_dims, any n <= batch_capacity, output [n][width] (AoS) or
-// [width][n] (SoA) in the requested precision, unpadded; no parameters (null params / dL_dparams are fine)
-static NeusModule* make_pf_module(uint32_t n_input_dims, const JsonValue& j, int requested_precision, uint32_t batch_capacity) {
-	if (batch_capacity == 0 || batch_capacity % 128 != 0 || batch_capacity > (1u << 24))
-		throw std::runtime_error("batch_capacity must be a positive multiple of 128 (<= 2^24)");
-	if (requested_precision != NEUS_PRECISION_FP32 && requested_precision != NEUS_PRECISION_FP16)
-		throw std::runtime_error("create_encoding: requested_precision must be NEUS_PRECISION_FP32 or NEUS_PRECISION_FP16");
-	const PfEnc E = pf_from_json(j, n_input_dims);
-	const std::string ol = j.string("output_layout", "AoS");
-	if (ol == "paired") throw std::runtime_error("parameter-free encoding: output_layout AoS or SoA (paired is the HashGrid kernels' layout)");
-	int dev = 0;
-	HIP_CHECK(hipGetDevice(&dev));
-	auto m = std::make_unique<NeusModule>(dev);
-	m->kind = NeusModule::PfEncoding;
-	module_options(m.get(), j);
-	m->f32 = requested_precision == NEUS_PRECISION_FP32;
-	m->pf = E;
-	m->n_in = E.n_in; m->n_out = E.width;
-	m->capacity = batch_capacity;
-	m->hyper = "{" + pf_hyper_members(E, j.string("otype", "") == "Composite") + ", \"n_input_dims\": " + std::to_string(E.n_in) +
-	           ", \"output_layout\": \"" + (m->layout == ENC_LAYOUT_SOA ? "SoA" : "AoS") + "\", \"gradient_precision\": \"" +
-	           (m->grad_fp16 ? "fp16" : "fp32") + "\", \"precision\": \"" + (m->f32 ? "fp32" : "fp16") + "\"}";
-	HIP_CHECK(hipStreamSynchronize(m->core.stream));
-	return m.release();
-}
-
-// The grid otypes and what decides between the existing 3-D kernels and the general grid (grid_nd.hip). Host only.
-static bool grid_otype(const std::string& ot) { return ot == "HashGrid" || ot == "Grid" || ot == "DenseGrid" || ot == "TiledGrid"; }
+// The grid otypes and what decides between the 3-D 2-feature kernels and the general grid (grid_nd.hip). Host only.
+bool grid_otype(const std::string& ot) { return ot == "HashGrid" || ot == "Grid" || ot == "DenseGrid" || ot == "TiledGrid"; }
 struct GridChoice { bool general; uint32_t type; bool smooth; };
-static GridChoice grid_choice(const JsonValue& j, uint32_t n_input_dims) {
+GridChoice grid_choice(const JsonValue& j, uint32_t n_input_dims) {
 	const std::string ot = j.string("otype", "HashGrid");
 	const std::string ty = j.string("type", ot == "DenseGrid" ? "Dense" : (ot == "TiledGrid" ? "Tiled" : "Hash"));
 	GridChoice c{};
@@ -3561,366 +3508,537 @@ static GridChoice grid_choice(const JsonValue& j, uint32_t n_input_dims) {
 	c.general = im == "general" || n_input_dims != 3 || nf != 2 || c.type != GRID_ND_HASH || c.smooth;
 	return c;
 }
-// the general grid's tables and progressive-level settings into the module (no Testbed network is set up)
-static void nd_setup_module(NeusModule* m, const JsonValue& j, uint32_t n_input_dims, const GridChoice& gc, uint32_t batch_capacity) {
+
+// a tensor of an encoding operation: ld = 0: the caller's (the stand-alone encoding's output, dL_doutput or dL_ddLdoutput in
+// the module's layout and precision); ld > 0: fp16 rows [n][ld] of the network (features in columns [0, width))
+struct EncIO { void* p; uint32_t ld; };
+EncIO enc_io(const void* p, uint32_t ld) { return EncIO{const_cast<void*>(p), ld}; }
+
+// what the create-time parser decides, host only (enc_from_json)
+struct EncSpec {
+	enum Type { Identity, Pf, Hash16, Hash32, Nd } type = Identity;
+	uint32_t n_in = 0;
+	float scale = 1.f, offset = 0.f;  // Identity in front of a network (identity.h:44-70)
+	PfEnc pf{};                       // Pf: the segments
+	bool composite = false;
+	GridChoice gc{};                  // Nd
+	NeusNetworkConfig cfg{};          // the grids: levels, table sizes, progressive-level settings
+	uint32_t width() const {
+		switch (type) {
+		case Identity: return n_in;
+		case Pf: return pf.width;
+		default: return cfg.n_features_per_level * cfg.n_levels;
+		}
+	}
+};
+
+struct Enc : EncSpec {
+	NeusTestbed* core = nullptr;      // the grids: tables (gl), layout, progressive-level settings, scatter workspace
+	GridNd nd{};                      // Nd: the level tables
+	uint32_t capacity = 0;
+	// stand-alone output layout (ENC_LAYOUT_*): AoS [n][width] = the column-major matrix tcnn's cpp::Module wraps around the
+	// caller's buffer (cpp_api.cu:58-70); SoA [width][n] = GridEncoding::preferred_output_layout (grid.h:2357-2359);
+	// paired [L][n] half2 = features 2l, 2l+1 of level l adjacent, the fp16 HashGrid kernels' own
+	uint32_t layout = ENC_LAYOUT_AOS;
+	bool f32 = false;                 // stand-alone with requested_precision fp32: float params / output / gradients
+	int training_step = 0;            // GridEncoding::set_training_step (grid.h:2427-2437): 0 = every level
+	Dev<uint32_t> enc_tmp, denc_tmp;  // Hash16: paired-layout staging of non-paired I/O
+	Dev<uint32_t> u_tmp;              // Hash16 in front of a network: dy/dx . dL_ddLdinput, paired
+	Dev<float4> v4, zero_v;           // Hash16: dL_ddLdinput as float4 / the scatter's absent second-order term
+	Dev<half_t> zero_h;
+	Dev<float> partial;               // the grids: dL_dinput's per-level terms [n_in L][capacity] (first use)
+
+	// ---- description
+	bool keeps_dydx() const { return type == Hash16 || type == Hash32; }
+	uint32_t L() const { return core->lay.L; }
+	uint32_t valid() const { return core->valid_level_at(training_step); }
+	uint64_t n_params() const {
+		switch (type) {
+		case Hash16: case Hash32: return core->lay.n_grid;
+		case Nd: return (uint64_t)nd.gl.offset[nd.gl.n_levels] * nd.F;
+		default: return 0;
+		}
+	}
+	// the accepted config back as JSON members (no braces): the otype with its own keys, nested types included
+	std::string hyper_members(bool standalone) const {
+		const NeusNetworkConfig& c = core->cfg;
+		switch (type) {
+		case Identity: return "\"otype\": \"Identity\", \"scale\": " + fmt_float(scale) + ", \"offset\": " + fmt_float(offset);
+		case Pf: {
+			if (!composite) return pf_hyper_segment(pf.seg[0]);
+			std::string s = "\"otype\": \"Composite\", \"nested\": [";
+			for (uint32_t q = 0; q < pf.n_seg; ++q)
+				s += std::string(q ? ", " : "") + "{\"n_dims_to_encode\": " + std::to_string(pf.seg[q].dims) + ", " + pf_hyper_segment(pf.seg[q]) + "}";
+			return s + "]";
+		}
+		case Nd: {
+			static const char* tn[3] = {"Hash", "Dense", "Tiled"};
+			return "\"otype\": \"Grid\", \"type\": \"" + std::string(tn[nd.type]) + "\", \"n_input_dims\": " + std::to_string(nd.D) + ", \"n_levels\": " +
+			       std::to_string(c.n_levels) + ", \"n_features_per_level\": " + std::to_string(nd.F) + ", \"log2_hashmap_size\": " +
+			       std::to_string(c.log2_hashmap_size) + ", \"base_resolution\": " + std::to_string(c.base_resolution) + ", \"per_level_scale\": " +
+			       fmt_float(c.per_level_scale) + ", \"interpolation\": \"" + (nd.smooth ? "Smoothstep" : "Linear") + "\", \"valid_level_scale\": " +
+			       fmt_float(c.valid_level_scale) + ", \"base_valid_level_scale\": " + fmt_float(c.base_valid_level_scale) + ", \"base_training_step\": " +
+			       std::to_string(c.base_training_step);
+		}
+		default: {  // in front of a network the progressive-level settings are not echoed
+			const std::string s = "\"otype\": \"HashGrid\", \"n_levels\": " + std::to_string(c.n_levels) + ", \"n_features_per_level\": 2, \"log2_hashmap_size\": " +
+			                      std::to_string(c.log2_hashmap_size) + ", \"base_resolution\": " + std::to_string(c.base_resolution) +
+			                      ", \"per_level_scale\": " + fmt_float(c.per_level_scale);
+			if (!standalone) return s;
+			return s + ", \"valid_level_scale\": " + fmt_float(c.valid_level_scale) + ", \"base_valid_level_scale\": " + fmt_float(c.base_valid_level_scale) +
+			       ", \"base_training_step\": " + std::to_string(c.base_training_step);
+		}
+		}
+	}
+	// the module's own "n_input_dims" member: the HashGrid has none (3), the stand-alone general grid echoes it among its own
+	std::string hyper_dims(bool standalone) const {
+		if (keeps_dydx() || (standalone && type == Nd)) return "";
+		return ", \"n_input_dims\": " + std::to_string(n_in);
+	}
+	// tables and workspace (`standalone`: the I/O is the caller's, in `layout`; otherwise a network's rows or k_dnet's paired input)
+	void setup(uint32_t cap, bool standalone) {
+		capacity = cap;
+		switch (type) {
+		case Hash16:
+			core->setup_network(cfg, nullptr, false);
+			v4.alloc(cap); zero_h.alloc((size_t)2 * L() * cap); zero_v.alloc(cap);
+			if (!standalone || layout != ENC_LAYOUT_PAIRED) { enc_tmp.alloc((size_t)L() * cap); denc_tmp.alloc((size_t)L() * cap); }
+			if (!standalone) u_tmp.alloc((size_t)L() * cap);
+			HIP_CHECK(hipMemset(zero_h.p, 0, zero_h.n * sizeof(half_t)));
+			HIP_CHECK(hipMemset(zero_v.p, 0, zero_v.n * sizeof(float4)));
+			break;
+		case Hash32: core->setup_network(cfg, nullptr, false); break;
+		case Nd:  // no Testbed network is set up: the tables, and the progressive-level settings for valid_level_at
+			nd = make_grid_nd(n_in, cfg.n_features_per_level, gc.type, gc.smooth, cfg.n_levels, cfg.log2_hashmap_size, cfg.base_resolution, cfg.per_level_scale);
+			core->cfg = cfg;
+			core->lay.L = cfg.n_levels;
+			break;
+		default: break;
+		}
+	}
+	float* scratch() { partial.alloc((size_t)n_in * L() * capacity); return partial.p; }
+	// backward_backward_input's dL_dinput needs the encoding's second derivative: none is implemented for the spherical
+	// harmonics (nor has tcnn's SphericalHarmonicsEncoding a backward_backward_input)
+	void check_bbi_sh(const float* dL_dinput) const {
+		bool sh = false;
+		for (uint32_t q = 0; q < pf.n_seg; ++q) sh = sh || pf.seg[q].type == PF_SH;
+		if (dL_dinput && sh)
+			throw std::runtime_error("backward_backward_input: dL_dinput is not supported with a SphericalHarmonics segment (the second "
+			                         "derivative of the spherical harmonics is not implemented); dL_ddLdoutput and the parameter gradients are");
+	}
+	// the pointers backward_backward_input needs beside dL_ddLdinput (a network in front asks for dL_doutput and params itself)
+	bool bbi_args(const float* input, const void* dL_doutput, const void* params, const float* dL_dinput) const {
+		if (type == Identity) return true;
+		if (type == Pf) return input && (dL_doutput || !dL_dinput);
+		return input && dL_doutput && (params || type != Nd);
+	}
+	// backward_backward reads dL/d(encoding output) for its parameter gradient and for dL_dinput; Identity has neither
+	bool bbi_reads_dy(const float* g, const float* dL_dinput) const { return type != Identity && (g || dL_dinput); }
+	// where the network's backward puts dL/d(its input): rows for this encoding's backward; Identity is the network's own input stage
+	FfSink sink(float* dL_dinput) const { return FfSink{type == Identity, dL_dinput, scale}; }
+	// what backward needs of the context and the call, checked before the first launch
+	void check_backward(const NeusContext* ctx, const void* params, const float* dL_dinput, bool standalone) const {
+		if (keeps_dydx() && !standalone && !ctx->dydx.p) throw std::runtime_error("module backward: the context is not from this module's forward");
+		if (keeps_dydx() && dL_dinput && !ctx->dydx.p) throw std::runtime_error("encoding backward: dL_dinput needs the forward's dy/dx");
+		if (type == Nd && dL_dinput && !params) throw std::runtime_error("module: null params");
+	}
+
+	// ---- tensors
+	// a tensor of the parameter-free encodings' and the general grid's kernels: unpadded AoS / SoA, or the network's rows
+	PfView view(EncIO t, uint32_t n) const {
+		if (t.ld) return PfView{t.p, t.ld, 1, 0u};
+		return layout == ENC_LAYOUT_SOA ? PfView{t.p, 1, n, f32 ? 1u : 0u} : PfView{t.p, width(), 1, f32 ? 1u : 0u};
+	}
+	uint32_t pad(EncIO t) const { return t.ld ? t.ld - width() : 0; }  // the rows' padding columns (zero, grid.h:1540-1550)
+	// ---- the fp16 HashGrid's steps (also the fused k_dnet network's)
+	// the stand-alone encoding's per-call copy of params into the core's buffer
+	const half_t* load_params(const void* params, hipStream_t s) {
+		if (!params) throw std::runtime_error("module: null params");
+		half_t* grid = core->params_h.p + core->lay.grid_off;
+		HIP_CHECK(hipMemcpyAsync(grid, params, (size_t)core->lay.n_grid * 2, hipMemcpyDeviceToDevice, s));
+		return grid;
+	}
+	// a caller-layout dL_doutput as the kernels' paired layout
+	const half_t* paired_in(const void* x, uint32_t n, hipStream_t s) {
+		if (layout == ENC_LAYOUT_PAIRED) return (const half_t*)x;
+		launch_enc_from_layout(s, n, L(), (const half_t*)x, layout, denc_tmp.p);
+		return (const half_t*)denc_tmp.p;
+	}
+	// the paired encoding in front of a network: kept in the context of a forward
+	uint32_t* paired_out(NeusContext* ctx, uint32_t n) {
+		if (!ctx) return enc_tmp.p;
+		ctx->enc.alloc((size_t)L() * std::max(1u, n));
+		return ctx->enc.p;
+	}
+	// kernel_grid (grid.h) into the paired layout; a forward's context keeps dy/dx for dL_dinput and second order
+	void hash_encode(hipStream_t s, uint32_t n, const float* input, const half_t* grid, NeusContext* ctx, uint32_t* paired) {
+		float* dydx = nullptr;
+		if (ctx) { ctx->dydx.alloc((size_t)6 * L() * std::max(1u, n)); dydx = ctx->dydx.p; }
+		const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((n + 255) / 256, 4096));
+		launch_grid_encode(s, nullptr, n, n, input, 3, core->gl, valid(), grid, paired, dydx, gx);
+	}
+	// the fused binned scatter: kernel_grid_backward (grid.h:371-500) with (first = dL_doutput, second = zero_h, v = zero_v);
+	// kernel_grid_backward_input_backward_grid (grid.h:880-1007) with (zero_h, dL_doutput, v4 = dL_ddLdinput)
+	void hash_scatter(hipStream_t s, uint32_t n, const float* input, const half_t* first, const half_t* second, const float4* v, float* g) {
+		launch_grid_scatter(s, nullptr, n, n, input, 3, core->gl, valid(), first, second, v, g, core->swork, core->scan_tmp.p, core->scan_tmp_bytes);
+	}
+	// kernel_grid_backward_input_backward_input (grid.h:1010-1181)
+	void hash_ddx(hipStream_t s, uint32_t n, const float* input, const half_t* grid, const half_t* dly, const float* u, float* dL_dinput) {
+		launch_grid_ddx(s, n, n, input, core->gl, valid(), grid, dly, u, scratch(), dL_dinput);
+	}
+
+	// ---- operations. params: the encoding's own (behind the network's)
+	// input -> out; a forward's context is filled where the variant keeps one
+	void encode(hipStream_t s, uint32_t n, const float* input, const void* params, NeusContext* ctx, EncIO out) {
+		switch (type) {
+		case Identity:  // padded to the rows' width with ones (identity.h:44-70)
+			launch_ff_input(s, n, n_in, out.ld, input, scale, offset, (half_t*)out.p, false);
+			break;
+		case Pf:  // rows: padded with ones, as tcnn's encodings pad
+			if (out.ld) launch_pf_rows(s, pf, n, input, nullptr, (half_t*)out.p, out.ld);
+			else launch_pf_out(s, pf, n, input, nullptr, view(out, n));
+			break;
+		case Hash16:
+			if (out.ld) {  // zero-padded to the MLP's input width (grid.h:1540-1550)
+				uint32_t* enc = paired_out(ctx, n);
+				hash_encode(s, n, input, (const half_t*)params, ctx, enc);
+				launch_enc_to_rows(s, n, L(), enc, (half_t*)out.p, out.ld);
+			} else {
+				const half_t* grid = load_params(params, s);
+				uint32_t* enc = layout == ENC_LAYOUT_PAIRED ? (uint32_t*)out.p : enc_tmp.p;
+				hash_encode(s, n, input, grid, ctx, enc);
+				if (layout != ENC_LAYOUT_PAIRED) launch_enc_to_layout(s, n, L(), enc, (half_t*)out.p, layout);
+			}
+			break;
+		case Hash32: {  // GridEncoding<float>::forward (kernel_grid with T = float)
+			float* dydx = nullptr;
+			if (ctx) { ctx->dydx.alloc((size_t)6 * L() * std::max(1u, n)); dydx = ctx->dydx.p; }
+			launch_grid_f32_forward(s, n, core->gl, valid(), input, (const float*)params, (float*)out.p, layout, dydx);
+			break;
+		}
+		case Nd:
+			launch_grid_nd_forward(s, n, nd, valid(), input, params, !out.ld && f32, view(out, n), pad(out));
+			break;
+		}
+	}
+	// dy = dL/d(encoding output), the caller's dL_doutput or the network's dL/dX0 rows: the parameter gradient into g (this
+	// encoding's part of the module's; null: skipped) and dL_dinput = J^T dy (null: skipped)
+	void backward(hipStream_t s, uint32_t n, const NeusContext* ctx, const float* input, EncIO dy, const void* params, float* g, float* dL_dinput) {
+		switch (type) {
+		case Identity: break;  // no parameters; the network's layer 0 wrote dL_dinput (FfSink)
+		case Pf:  // the Jacobian recomputed from the input
+			if (dL_dinput) launch_pf_input_grad(s, pf, n, input, view(dy, n), nullptr, dL_dinput);
+			break;
+		case Hash16: {  // the grid gradient through the fused binned scatter, second-order term zero; dL_dinput from dy/dx
+			const half_t* dly = (const half_t*)denc_tmp.p;
+			if (dy.ld) launch_enc_from_rows(s, n, L(), (const half_t*)dy.p, dy.ld, denc_tmp.p);
+			else { load_params(params, s); dly = paired_in(dy.p, n, s); }
+			if (!dy.ld && dL_dinput) launch_enc_input_grad(s, n, n, L(), dly, ctx->dydx.p, dL_dinput, 3);
+			if (g) hash_scatter(s, n, input, dly, zero_h.p, zero_v.p, g);
+			if (dy.ld && dL_dinput) launch_enc_input_grad(s, n, n, L(), dly, ctx->dydx.p, dL_dinput, 3);
+			break;
+		}
+		case Hash32:  // GridEncoding<float>::backward: kernel_grid_backward (float atomics) and dL_dinput from dy/dx
+			if (g) HIP_CHECK(hipMemsetAsync(g, 0, (size_t)n_params() * 4, s));
+			launch_grid_f32_backward(s, n, core->gl, valid(), input, (const float*)dy.p, layout, g, ctx->dydx.p, dL_dinput);
+			break;
+		case Nd:  // kernel_grid_backward by fp32 atomics into a zeroed buffer; dL_dinput with the Jacobian gathered again from the input
+			if (g) {
+				HIP_CHECK(hipMemsetAsync(g, 0, (size_t)n_params() * 4, s));
+				launch_grid_nd_backward(s, n, nd, valid(), input, view(dy, n), g);
+			}
+			if (dL_dinput) launch_grid_nd_input_grad(s, n, nd, valid(), input, params, !dy.ld && f32, view(dy, n), scratch(), dL_dinput);
+			break;
+		}
+	}
+	// GridEncoding::backward_backward_input (grid.h:880-1181) and its parameter-free counterparts. u = dL_ddLdinput, dy =
+	// dL/d(encoding output): the second-order parameter gradient into g, J u into Ju (the caller's dL_ddLdoutput or the
+	// network's front rows) and dL_dinput; each is skipped when null
+	void backward_backward(hipStream_t s, uint32_t n, const NeusContext* ctx, const float* input, const float* u, EncIO dy, const void* params, float* g,
+	                       EncIO Ju, float* dL_dinput) {
+		switch (type) {
+		case Identity:
+			// identity.h:182-206: the network's dL_ddLdinput = scale x u (the padded rows, which the reference leaves uninitialised,
+			// are 0: the constant padding has no input gradient); dL_dinput = 0: with act'' = 0 the first derivative is piecewise
+			// constant in the input
+			if (dL_dinput) HIP_CHECK(hipMemsetAsync(dL_dinput, 0, (size_t)n * n_in * 4, s));
+			if (Ju.p) launch_ff_input(s, n, n_in, Ju.ld, u, scale, 0.f, (half_t*)Ju.p, true);
+			break;
+		case Pf:
+			// J u from first derivatives only; dL_dinput_d = u_d sum_k dy_k d2y_k/dx_d^2 (every feature depends on one input dim,
+			// except the spherical harmonics': refused)
+			if (dL_dinput) launch_pf_input_grad(s, pf, n, input, view(dy, n), u, dL_dinput);
+			if (Ju.p && Ju.ld) launch_pf_rows(s, pf, n, input, u, (half_t*)Ju.p, Ju.ld);
+			else if (Ju.p) launch_pf_out(s, pf, n, input, u, view(Ju, n));
+			break;
+		case Hash16:
+			// pos_encoding_dy = dy/dx . u (kernel_grid_backward_input_backward_dLdoutput, grid.h:1697-1800; also u as float4 for the
+			// scatter), the second-order grid gradient and the grid's second derivative in x
+			if (Ju.ld) {
+				const half_t* dly = (const half_t*)denc_tmp.p;
+				if (dy.p) launch_enc_from_rows(s, n, L(), (const half_t*)dy.p, dy.ld, denc_tmp.p);
+				if (g || Ju.p) launch_enc_ddLdoutput(s, n, n, L(), u, ctx->dydx.p, (half_t*)u_tmp.p, v4.p);
+				if (g) hash_scatter(s, n, input, zero_h.p, dly, v4.p, g);
+				if (dL_dinput) hash_ddx(s, n, input, (const half_t*)params, dly, u, dL_dinput);
+				if (Ju.p) launch_enc_to_rows(s, n, L(), u_tmp.p, (half_t*)Ju.p, Ju.ld);
+			} else {
+				const bool relay = layout != ENC_LAYOUT_PAIRED && Ju.p;
+				launch_enc_ddLdoutput(s, n, n, L(), u, ctx->dydx.p, relay ? (half_t*)enc_tmp.p : (half_t*)Ju.p, v4.p);
+				if (relay) launch_enc_to_layout(s, n, L(), enc_tmp.p, (half_t*)Ju.p, layout);
+				if (g || dL_dinput) {
+					const half_t* grid = load_params(params, s);
+					const half_t* dly = paired_in(dy.p, n, s);
+					if (g) hash_scatter(s, n, input, zero_h.p, dly, v4.p, g);
+					if (dL_dinput) hash_ddx(s, n, input, grid, dly, u, dL_dinput);
+				}
+			}
+			break;
+		case Hash32:  // GridEncoding<float>::backward_backward_input (grid.h:880-1007 with GRAD_T = float; grid.h:1010-1181)
+			if (dL_dinput && !params) throw std::runtime_error("module: null params");
+			if (g) HIP_CHECK(hipMemsetAsync(g, 0, (size_t)n_params() * 4, s));
+			launch_grid_f32_bbi(s, n, core->gl, valid(), input, u, (const float*)dy.p, layout, g, ctx->dydx.p, (float*)Ju.p);
+			if (dL_dinput) launch_grid_f32_ddx(s, n, core->gl, valid(), input, (const float*)params, (const float*)dy.p, layout, u, scratch(), dL_dinput);
+			break;
+		case Nd:  // one launch: atomics into a zeroed buffer, J u, and dL_dinput (mixed terms, and the diagonal ones with Smoothstep)
+			if (g) HIP_CHECK(hipMemsetAsync(g, 0, (size_t)n_params() * 4, s));
+			launch_grid_nd_bbi(s, n, nd, valid(), input, params, !Ju.ld && f32, u, view(dy, n), g, view(Ju, n), pad(Ju), dL_dinput ? scratch() : nullptr,
+			                   dL_dinput);
+			break;
+		}
+	}
+};
+
+// The create-time parser of the encoding part (`with_net`: in front of a network, where Identity is the MLP's own input
+// stage). Host only: every check runs before a device call.
+EncSpec enc_from_json(const JsonValue& j, uint32_t n_input_dims, uint32_t batch_capacity, bool with_net) {
+	EncSpec e;
+	const std::string ot = j.string("otype", "HashGrid");
+	e.n_in = n_input_dims;
+	if (with_net && ot == "Identity") {
+		e.type = EncSpec::Identity; e.scale = (float)j.number("scale", 1.0); e.offset = (float)j.number("offset", 0.0);
+		return e;
+	}
+	if (pf_otype(ot)) {
+		e.type = EncSpec::Pf; e.pf = pf_from_json(j, n_input_dims); e.composite = ot == "Composite";
+		return e;
+	}
+	if (!grid_otype(ot))
+		throw std::runtime_error(with_net ? "network with input encoding: the encoding must be Identity, Frequency, SphericalHarmonics, Composite or "
+		                                    "a grid (HashGrid / Grid / DenseGrid / TiledGrid) on gfx950"
+		                                  : "encoding module: HashGrid / Grid / DenseGrid / TiledGrid, Identity, Frequency, SphericalHarmonics and Composite "
+		                                    "are implemented on gfx950");
+	e.gc = grid_choice(j, n_input_dims);
+	e.type = e.gc.general ? EncSpec::Nd : EncSpec::Hash16;
 	JsonValue none; none.kind = JsonValue::Object;
-	NeusNetworkConfig c = module_config(j, none, none, batch_capacity, true);
-	if (c.n_levels == 0 || c.n_levels > MAX_LEVELS) throw std::runtime_error("grid encoding: 1..16 levels supported");
-	m->nd = make_grid_nd(n_input_dims, c.n_features_per_level, gc.type, gc.smooth, c.n_levels, c.log2_hashmap_size, c.base_resolution, c.per_level_scale);
-	m->core.cfg = c;
-	m->core.lay.L = c.n_levels;
-	m->n_in = n_input_dims;
-}
-static std::string nd_hyper_members(const NeusModule* m) {
-	static const char* tn[3] = {"Hash", "Dense", "Tiled"};
-	const NeusNetworkConfig& c = m->core.cfg;
-	return "\"otype\": \"Grid\", \"type\": \"" + std::string(tn[m->nd.type]) + "\", \"n_input_dims\": " + std::to_string(m->nd.D) + ", \"n_levels\": " +
-	       std::to_string(c.n_levels) + ", \"n_features_per_level\": " + std::to_string(m->nd.F) + ", \"log2_hashmap_size\": " +
-	       std::to_string(c.log2_hashmap_size) + ", \"base_resolution\": " + std::to_string(c.base_resolution) + ", \"per_level_scale\": " +
-	       fmt_float(c.per_level_scale) + ", \"interpolation\": \"" + (m->nd.smooth ? "Smoothstep" : "Linear") + "\", \"valid_level_scale\": " +
-	       fmt_float(c.valid_level_scale) + ", \"base_valid_level_scale\": " + fmt_float(c.base_valid_level_scale) + ", \"base_training_step\": " +
-	       std::to_string(c.base_training_step);
+	e.cfg = module_config(j, none, none, batch_capacity, true);
+	if (with_net && e.gc.general && (uint64_t)e.cfg.n_levels * e.cfg.n_features_per_level > 128)
+		throw std::runtime_error("network with input encoding: the grid's encoded width n_features_per_level * n_levels = " +
+		                         std::to_string((uint64_t)e.cfg.n_levels * e.cfg.n_features_per_level) +
+		                         " exceeds the 128 input dims of the FullyFusedMLP on gfx950");
+	if (e.cfg.n_levels == 0 || e.cfg.n_levels > MAX_LEVELS)
+		throw std::runtime_error(std::string(e.gc.general ? "grid encoding" : "GridEncoding") + ": 1..16 levels supported");
+	return e;
 }
 
+}  // namespace
+
+struct NeusModule {
+	// Composed: enc (and ff, when it has a network) through the shared path; the two fused specials: Nerf = the NeuS
+	// NerfNetwork on the core's own kernels, Dnet = HashGrid -> FullyFusedMLP(1 hidden ReLU layer, <= 16 linear outputs) on
+	// k_dnet, the network whose backward_backward_input tcnn implements (network_with_input_encoding.h:159-250,
+	// fully_fused_mlp.cu:1088-1198)
+	enum Fused { Composed = 0, Nerf = 1, Dnet = 2 } fused = Composed;
+	Enc enc;                     // Nerf: only its tag (a HashGrid) and training_step
+	FfNet ff;                    // P = 0: a stand-alone encoding; Dnet: the fused network's shape
+	FfWork fw;                   // Dnet: only k_dnet's per-block weight-gradient rows (partial) and dummy
+	NeusTestbed core;
+	uint32_t capacity = 0, n_in = 0, n_out = 0;
+	uint64_t P = 0;              // n_params = [network | encoding]
+	uint32_t enc_off = 0;        // the parameters ahead of the encoding's (neus_module_info's grid_offset)
+	uint32_t indeed_batch = 0;   // NeuS backward normalisation of the eikonal entries; 0 = the call's n
+	std::string hyper;
+	bool grad_fp16 = true;       // dL_dparams in param precision (fp16, trainer.h:72-109) or fp32
+	Dev<float> gtmp;             // gradients of an Accumulate call (and of every fp16-gradient call)
+	Dev<float4> dpos;            // Nerf: dL/dposition of net_backward
+	explicit NeusModule(int device) : core(device) { enc.core = &core; }
+	bool net() const { return fused == Composed && ff.P; }
+	const void* enc_params(const void* params) const { return (const half_t*)params + enc_off; }
+	void check_n(uint32_t n, bool backward) const {
+		if (n > capacity) throw std::runtime_error("module: n_elements exceeds the module's batch capacity");
+		if (backward && fused == Nerf && (n == 0 || n % 128 != 0))
+			throw std::runtime_error("module backward: n_elements must be a positive multiple of 128 (fully_fused_mlp.cu:779-781)");
+		if (net() && n % 128 != 0) throw std::runtime_error("FullyFusedMLP: batch size must be a multiple of 128 (fully_fused_mlp.cu:779-781)");
+	}
+	// the destination of this call's parameter gradients (Overwrite: dL_dparams itself; Accumulate: a scratch buffer); null
+	// with Ignore and for a module without parameters
+	float* grad_target(void* dL_dparams, int mode) {
+		if (!P || mode == NEUS_GRADIENT_IGNORE) return nullptr;
+		if (!dL_dparams) throw std::runtime_error("module: dL_dparams is null with a gradient mode other than Ignore");
+		if (mode != NEUS_GRADIENT_OVERWRITE && mode != NEUS_GRADIENT_ACCUMULATE) throw std::runtime_error("module: unknown gradient mode");
+		if (mode == NEUS_GRADIENT_OVERWRITE && !grad_fp16) return (float*)dL_dparams;
+		return gtmp.p;
+	}
+	// the epilogue of a call with parameter gradients: the network's weight gradients from its partials, then g into dL_dparams
+	void finish_grad(float* g, uint32_t n, void* dL_dparams, int mode, hipStream_t s) {
+		if (!g) return;
+		if (net()) ff_reduce(ff, fw, s, ff_wgrad_blocks(n), g);
+		if (grad_fp16) launch_grad_to_half(s, (uint32_t)P, gtmp.p, (half_t*)dL_dparams, mode == NEUS_GRADIENT_ACCUMULATE);
+		else if (mode == NEUS_GRADIENT_ACCUMULATE) launch_add_f32(s, (uint32_t)P, gtmp.p, (float*)dL_dparams);
+	}
+	// backward_backward_input's dL_ddLdoutput / dL_dinput of a network: the fronts / backs chain has no act'' term, so they
+	// are exact only where act'' = 0 (hidden ReLU or None) and the output is linear
+	void check_bbi_exact(const void* dL_ddLdoutput, const float* dL_dinput) const {
+		if (!ff.P || (!dL_ddLdoutput && !dL_dinput)) return;
+		if ((ff.act == FF_RELU || ff.act == FF_NONE) && ff.out_act == FF_NONE) return;
+		throw std::runtime_error("backward_backward_input: dL_ddLdoutput and dL_dinput are exact only for hidden activation ReLU or None with "
+		                         "output activation None (the second derivative of any other activation is not implemented); pass null "
+		                         "for both to get the parameter gradients alone");
+	}
+	// a context of this module's forward
+	bool ctx_ok(const NeusContext* ctx) const {
+		return (!enc.keeps_dydx() || ctx->dydx.p) && (!net() || ctx->acts.p) && (fused != Dnet || ctx->enc.p);
+	}
+};
+
+// ---------------------------------------------------------------- creation
+static void check_capacity(uint32_t batch_capacity) {
+	if (batch_capacity == 0 || batch_capacity % 128 != 0 || batch_capacity > (1u << 24))
+		throw std::runtime_error("batch_capacity must be a positive multiple of 128 (<= 2^24)");
+}
+// cpp_api.cu:174-180: Fp32 -> an encoding with float params, output and gradients, Fp16 -> __half
+static bool precision_f32(int requested_precision) {
+	if (requested_precision != NEUS_PRECISION_FP32 && requested_precision != NEUS_PRECISION_FP16)
+		throw std::runtime_error("create_encoding: requested_precision must be NEUS_PRECISION_FP32 or NEUS_PRECISION_FP16");
+	return requested_precision == NEUS_PRECISION_FP32;
+}
+// A module of the parsed parts with its options (this build's keys, beside tcnn's): "gradient_precision": "fp16" (default,
+// tcnn's param precision) | "fp32"; encoding "output_layout": "AoS" (default: cpp::Module's column-major view) | "SoA" | "paired"
+static std::unique_ptr<NeusModule> new_module(const EncSpec& e, const FfNet& f, const JsonValue& j, uint32_t batch_capacity) {
+	int dev = 0;
+	HIP_CHECK(hipGetDevice(&dev));
+	auto m = std::make_unique<NeusModule>(dev);
+	static_cast<EncSpec&>(m->enc) = e;
+	m->ff = f;
+	m->capacity = batch_capacity;
+	const std::string gp = j.string("gradient_precision", "fp16");
+	if (gp != "fp16" && gp != "fp32") throw std::runtime_error("module: gradient_precision must be fp16 or fp32");
+	m->grad_fp16 = gp == "fp16";
+	const std::string ol = j.string("output_layout", "AoS");
+	if (ol == "AoS") m->enc.layout = ENC_LAYOUT_AOS;
+	else if (ol == "SoA") m->enc.layout = ENC_LAYOUT_SOA;
+	else if (ol == "paired") m->enc.layout = ENC_LAYOUT_PAIRED;
+	else throw std::runtime_error("encoding module: output_layout must be AoS, SoA or paired");
+	return m;
+}
+static std::string hyper_gradient_precision(const NeusModule* m) {
+	return std::string(", \"gradient_precision\": \"") + (m->grad_fp16 ? "fp16" : "fp32") + "\"";
+}
+// the accepted config back as JSON: the encoding's members, the network's, and the common tail
+static std::string module_hyper(const NeusModule* m) {
+	static const char* lay_names[3] = {"AoS", "SoA", "paired"};
+	const Enc& e = m->enc;
+	if (!m->ff.P)
+		return "{" + e.hyper_members(true) + e.hyper_dims(true) + ", \"output_layout\": \"" + lay_names[e.layout] + "\"" + hyper_gradient_precision(m) +
+		       ", \"precision\": \"" + (e.f32 ? "fp32" : "fp16") + "\"}";
+	return "{\"otype\": \"NetworkWithInputEncoding\", \"encoding\": {" + e.hyper_members(false) + "}, \"network\": " + ff_hyper(m->ff) + e.hyper_dims(false) +
+	       ", \"n_output_dims\": " + std::to_string(m->ff.n_out) + hyper_gradient_precision(m) + "}";
+}
+// the parts are set: their tables and workspace, the sizes both are asked for, the hyper-parameters
+static NeusModule* module_finish(std::unique_ptr<NeusModule> m) {
+	const bool standalone = !m->ff.P;
+	m->enc.setup(m->capacity, standalone);
+	m->enc_off = m->ff.P;
+	m->P = m->enc_off + m->enc.n_params();
+	m->n_in = m->enc.n_in;
+	m->n_out = standalone ? m->enc.width() : m->ff.out_pad;  // cpp::Module::n_output_dims = the padded output width
+	m->gtmp.alloc(m->P);
+	if (m->fused == NeusModule::Dnet) { m->fw.partial.alloc((size_t)dnet_blocks(m->capacity) * m->ff.P); m->fw.dummy.alloc(4); }
+	else if (m->ff.P) m->fw.alloc(m->ff, m->capacity);
+	m->hyper = module_hyper(m.get());
+	HIP_CHECK(hipStreamSynchronize(m->core.stream));
+	return m.release();
+}
+
+int neus_module_create_nerf_network(const char* config_json, uint32_t batch_capacity, NeusModule** out) {
+	return guard([&] {
+		if (!config_json || !out) throw std::runtime_error("neus_module_create_nerf_network: null argument");
+		check_capacity(batch_capacity);
+		const JsonValue j = parse_json(config_json);
+		EncSpec e;
+		e.type = EncSpec::Hash16;
+		auto m = new_module(e, FfNet{}, j, batch_capacity);
+		m->fused = NeusModule::Nerf;
+		m->enc.layout = ENC_LAYOUT_AOS;
+		m->core.setup_network(module_config(j.object("encoding"), j.object("network"), j.object("rgb_network"), batch_capacity), nullptr);
+		m->n_in = COORD_W; m->n_out = OUT_W;
+		m->P = m->core.lay.P; m->enc_off = m->core.lay.grid_off;
+		const NeusNetworkConfig& c = m->core.cfg;
+		m->hyper = "{\"otype\": \"NerfNetwork\", \"n_levels\": " + std::to_string(c.n_levels) + ", \"n_neurons\": " + std::to_string(c.n_neurons) +
+		           ", \"log2_hashmap_size\": " + std::to_string(c.log2_hashmap_size) + ", \"per_level_scale\": " + fmt_float(c.per_level_scale) +
+		           hyper_gradient_precision(m.get()) + "}";
+		m->gtmp.alloc(m->P);
+		m->dpos.alloc(batch_capacity);
+		HIP_CHECK(hipStreamSynchronize(m->core.stream));
+		*out = m.release();
+	});
+}
+
+// create_encoding: a parameter-free encoding (any n_input_dims), the HashGrid (3 inputs, 2 features; fp32: GridEncoding<float>)
+// or the general grid; any n <= batch_capacity, output [n][width] (AoS) or [width][n] (SoA) in the requested precision,
+// unpadded (the fp16 HashGrid also paired)
 int neus_module_create_encoding(uint32_t n_input_dims, const char* encoding_json, int requested_precision, uint32_t batch_capacity,
                                 NeusModule** out) {
 	return guard([&] {
 		if (!encoding_json || !out) throw std::runtime_error("neus_module_create_encoding: null argument");
 		const JsonValue j = parse_json(encoding_json);
-		const std::string ot = j.string("otype", "HashGrid");
-		if (pf_otype(ot)) {
-			*out = make_pf_module(n_input_dims, j, requested_precision, batch_capacity);
-			return;
+		check_capacity(batch_capacity);
+		const bool f32 = precision_f32(requested_precision);
+		EncSpec e = enc_from_json(j, n_input_dims, batch_capacity, false);
+		if (j.string("output_layout", "AoS") == "paired") {
+			if (e.type == EncSpec::Pf) throw std::runtime_error("parameter-free encoding: output_layout AoS or SoA (paired is the HashGrid kernels' layout)");
+			if (e.type == EncSpec::Nd) throw std::runtime_error("general grid encoding: output_layout AoS or SoA (paired is the 3-D, 2-feature fp16 kernels' layout)");
+			if (f32) throw std::runtime_error("fp32 HashGrid: output_layout AoS or SoA (paired is the fp16 kernels' layout)");
 		}
-		if (!grid_otype(ot))
-			throw std::runtime_error("encoding module: HashGrid / Grid / DenseGrid / TiledGrid, Identity, Frequency, SphericalHarmonics and Composite "
-			                         "are implemented on gfx950");
-		if (batch_capacity == 0 || batch_capacity % 128 != 0 || batch_capacity > (1u << 24))
-			throw std::runtime_error("batch_capacity must be a positive multiple of 128 (<= 2^24)");
-		const GridChoice gc = grid_choice(j, n_input_dims);
-		if (gc.general) {
-			// the general grid (grid_nd.hip): any n <= batch_capacity, output [n][F L] (AoS) or [F L][n] (SoA) in the requested
-			// precision; every check runs before a device call
-			if (requested_precision != NEUS_PRECISION_FP32 && requested_precision != NEUS_PRECISION_FP16)
-				throw std::runtime_error("create_encoding: requested_precision must be NEUS_PRECISION_FP32 or NEUS_PRECISION_FP16");
-			if (j.string("output_layout", "AoS") == "paired")
-				throw std::runtime_error("general grid encoding: output_layout AoS or SoA (paired is the 3-D, 2-feature fp16 kernels' layout)");
-			int dev = 0;
-			HIP_CHECK(hipGetDevice(&dev));
-			auto m = std::make_unique<NeusModule>(dev);
-			m->kind = NeusModule::NdGrid;
-			module_options(m.get(), j);
-			m->f32 = requested_precision == NEUS_PRECISION_FP32;
-			if (m->f32) m->grad_fp16 = false;
-			nd_setup_module(m.get(), j, n_input_dims, gc, batch_capacity);
-			m->n_out = m->n_out_nd();
-			m->capacity = batch_capacity;
-			m->gtmp.alloc(m->n_params());
-			m->hyper = "{" + nd_hyper_members(m.get()) + ", \"output_layout\": \"" + (m->layout == ENC_LAYOUT_SOA ? "SoA" : "AoS") +
-			           "\", \"gradient_precision\": \"" + (m->grad_fp16 ? "fp16" : "fp32") + "\", \"precision\": \"" + (m->f32 ? "fp32" : "fp16") + "\"}";
-			HIP_CHECK(hipStreamSynchronize(m->core.stream));
-			*out = m.release();
-			return;
-		}
-		int dev = 0;
-		HIP_CHECK(hipGetDevice(&dev));
-		auto m = std::make_unique<NeusModule>(dev);
-		m->kind = NeusModule::Encoding;
-		module_options(m.get(), j);
-		// cpp_api.cu:174-180: Fp32 -> GridEncoding<float> (float params, output and gradients), Fp16 -> GridEncoding<__half>
-		if (requested_precision != NEUS_PRECISION_FP32 && requested_precision != NEUS_PRECISION_FP16)
-			throw std::runtime_error("create_encoding: requested_precision must be NEUS_PRECISION_FP32 or NEUS_PRECISION_FP16");
-		m->f32 = requested_precision == NEUS_PRECISION_FP32;
-		if (m->f32) {
-			if (m->layout == ENC_LAYOUT_PAIRED) throw std::runtime_error("fp32 HashGrid: output_layout AoS or SoA (paired is the fp16 kernels' layout)");
-			m->grad_fp16 = false;
-		}
-		JsonValue none; none.kind = JsonValue::Object;
-		m->core.setup_network(module_config(j, none, none, batch_capacity, true), nullptr, false);
-		m->n_in = 3; m->n_out = 2 * m->core.lay.L;
-		const NeusNetworkConfig& c = m->core.cfg;
-		static const char* lay_names[3] = {"AoS", "SoA", "paired"};
-		m->hyper = "{\"otype\": \"HashGrid\", \"n_levels\": " + std::to_string(c.n_levels) + ", \"n_features_per_level\": 2, \"log2_hashmap_size\": " +
-		           std::to_string(c.log2_hashmap_size) + ", \"base_resolution\": " + std::to_string(c.base_resolution) + ", \"per_level_scale\": " +
-		           fmt_float(c.per_level_scale) + ", \"valid_level_scale\": " + fmt_float(c.valid_level_scale) + ", \"base_valid_level_scale\": " +
-		           fmt_float(c.base_valid_level_scale) + ", \"base_training_step\": " + std::to_string(c.base_training_step) +
-		           ", \"output_layout\": \"" + lay_names[m->layout] + "\", \"gradient_precision\": \"" + (m->grad_fp16 ? "fp16" : "fp32") +
-		           "\", \"precision\": \"" + (m->f32 ? "fp32" : "fp16") + "\"}";
-		module_common_init(m.get(), batch_capacity);
-		*out = m.release();
+		if (f32 && e.type == EncSpec::Hash16) e.type = EncSpec::Hash32;
+		auto m = new_module(e, FfNet{}, j, batch_capacity);
+		m->enc.f32 = f32;
+		if (f32 && e.type != EncSpec::Pf) m->grad_fp16 = false;  // float parameters: float gradients
+		*out = module_finish(std::move(m));
 	});
 }
 
-static std::string grid_hyper(const NeusNetworkConfig& c) {
-	return "{\"otype\": \"HashGrid\", \"n_levels\": " + std::to_string(c.n_levels) + ", \"n_features_per_level\": 2, \"log2_hashmap_size\": " +
-	       std::to_string(c.log2_hashmap_size) + ", \"base_resolution\": " + std::to_string(c.base_resolution) + ", \"per_level_scale\": " +
-	       fmt_float(c.per_level_scale) + "}";
-}
-static FfNet ff_from_json(const JsonValue& j, uint32_t n_input_dims, uint32_t n_output_dims);
-static std::string ff_hyper(const FfNet& f);
-static NeusModule* make_mlp_module(const FfNet& f, const JsonValue& j, uint32_t batch_capacity);
-// create_network_with_input_encoding (cpp_api.h:108; network_with_input_encoding.h): an Identity encoding (any input
-// width; scale / offset), a Frequency, SphericalHarmonics or Composite encoding (encodings.hip writes the MLP's input rows,
-// EncMlp) or a HashGrid (3 inputs) in front of a FullyFusedMLP of any depth, width 16 / 32 / 64 / 128 and activations.
-// The HashGrid -> one hidden ReLU layer -> linear network of width 16 / 64 runs on the fused k_dnet kernel; every other
-// HashGrid network is the encoding's kernels composed with ffmlp.hip's layers (GridMlp).
+// create_network_with_input_encoding (cpp_api.h:108; network_with_input_encoding.h): any encoding of create_encoding, or
+// Identity with scale / offset (any input width), in front of a FullyFusedMLP of any depth, width 16 / 32 / 64 / 128 and
+// activations. HashGrid -> one hidden ReLU layer -> linear network of width 16 / 64 runs on the fused k_dnet kernel.
 int neus_module_create_network_with_input_encoding(uint32_t n_input_dims, uint32_t n_output_dims, const char* encoding_json,
                                                    const char* network_json, uint32_t batch_capacity, NeusModule** out) {
 	return guard([&] {
 		if (!encoding_json || !network_json || !out) throw std::runtime_error("neus_module_create_network_with_input_encoding: null argument");
-		if (batch_capacity == 0 || batch_capacity % 128 != 0 || batch_capacity > (1u << 24))
-			throw std::runtime_error("batch_capacity must be a positive multiple of 128 (<= 2^24)");
+		check_capacity(batch_capacity);
 		const JsonValue je = parse_json(encoding_json), jn = parse_json(network_json);
-		const std::string ot = je.string("otype", "HashGrid");
-		if (ot == "Identity") {
-			FfNet f = ff_from_json(jn, n_input_dims, n_output_dims);
-			f.in_scale = (float)je.number("scale", 1.0);
-			f.in_offset = (float)je.number("offset", 0.0);
-			*out = make_mlp_module(f, jn, batch_capacity);
-			return;
-		}
-		if (pf_otype(ot)) {
-			const PfEnc E = pf_from_json(je, n_input_dims);
-			const FfNet f = ff_from_json(jn, E.width, n_output_dims);
-			NeusModule* m = make_mlp_module(f, jn, batch_capacity);
-			m->kind = NeusModule::EncMlp;
-			m->pf = E;
-			m->n_in = E.n_in;
-			m->hyper = "{\"otype\": \"NetworkWithInputEncoding\", \"encoding\": {" + pf_hyper_members(E, ot == "Composite") + "}, \"network\": " +
-			           ff_hyper(f) + ", \"n_input_dims\": " + std::to_string(E.n_in) + ", \"n_output_dims\": " + std::to_string(f.n_out) +
-			           ", \"gradient_precision\": \"" + (m->grad_fp16 ? "fp16" : "fp32") + "\"}";
-			*out = m;
-			return;
-		}
-		if (!grid_otype(ot))
-			throw std::runtime_error("network with input encoding: the encoding must be Identity, Frequency, SphericalHarmonics, Composite or "
-			                         "a grid (HashGrid / Grid / DenseGrid / TiledGrid) on gfx950");
-		const GridChoice gc = grid_choice(je, n_input_dims);
-		int dev = 0;
-		HIP_CHECK(hipGetDevice(&dev));
-		if (gc.general) {
-			// the general grid in front of a FullyFusedMLP (NdGridMlp): params [network | grid], the fused k_dnet route is not taken
-			auto m = std::make_unique<NeusModule>(dev);
-			m->kind = NeusModule::NdGridMlp;
-			module_options(m.get(), jn);
-			m->layout = ENC_LAYOUT_AOS;
-			{
-				JsonValue none; none.kind = JsonValue::Object;
-				const NeusNetworkConfig c = module_config(je, none, none, batch_capacity, true);
-				if ((uint64_t)c.n_levels * c.n_features_per_level > 128)
-					throw std::runtime_error("network with input encoding: the grid's encoded width n_features_per_level * n_levels = " +
-					                         std::to_string((uint64_t)c.n_levels * c.n_features_per_level) +
-					                         " exceeds the 128 input dims of the FullyFusedMLP on gfx950");
-			}
-			nd_setup_module(m.get(), je, n_input_dims, gc, batch_capacity);
-			const uint32_t width = m->n_out_nd();
-			const FfNet f = ff_from_json(jn, width, n_output_dims);
-			m->ff = f;
-			m->n_out = f.out_pad;
-			m->capacity = batch_capacity;
-			m->gtmp.alloc(m->n_params());
-			m->ff_acts.alloc(f.acts_halves(batch_capacity));
-			m->ff_front.alloc((size_t)batch_capacity * (f.in_pad + (size_t)f.N * f.W));
-			const uint32_t dmax = std::max(std::max(f.W, f.out_pad), f.in_pad);
-			m->ff_d[0].alloc((size_t)batch_capacity * dmax); m->ff_d[1].alloc((size_t)batch_capacity * dmax);
-			m->ff_partial.alloc((size_t)ff_wgrad_blocks(batch_capacity) * f.P);
-			m->ff_dummy.alloc(4);
-			m->hyper = "{\"otype\": \"NetworkWithInputEncoding\", \"encoding\": {" + nd_hyper_members(m.get()) + "}, \"network\": " + ff_hyper(f) +
-			           ", \"n_input_dims\": " + std::to_string(n_input_dims) + ", \"n_output_dims\": " + std::to_string(n_output_dims) +
-			           ", \"gradient_precision\": \"" + (m->grad_fp16 ? "fp16" : "fp32") + "\"}";
-			HIP_CHECK(hipStreamSynchronize(m->core.stream));
-			*out = m.release();
-			return;
-		}
-		auto m = std::make_unique<NeusModule>(dev);
-		module_options(m.get(), jn);
-		m->layout = ENC_LAYOUT_AOS;
-		JsonValue none; none.kind = JsonValue::Object;
-		m->core.setup_network(module_config(je, none, none, batch_capacity, true), nullptr, false);
-		const uint32_t L = m->core.lay.L;
-		const FfNet f = ff_from_json(jn, 2 * L, n_output_dims);
-		const bool fused = f.act == FF_RELU && f.out_act == FF_NONE && f.N == 1 && n_output_dims <= 16 && dnet_supported(L, f.W);
-		m->n_in = 3;
-		if (fused) {
-			m->kind = NeusModule::DensityNet;
-			m->dn_width = f.W;
-			m->dn_de = (2 * L + 15) / 16 * 16;
-			m->n_mlp = m->dn_width * m->dn_de + 16 * m->dn_width;
-			m->n_out = 16;
-		} else {
-			m->kind = NeusModule::GridMlp;
-			m->ff = f;
-			m->n_out = f.out_pad;
-		}
-		m->hyper = "{\"otype\": \"NetworkWithInputEncoding\", \"encoding\": " + grid_hyper(m->core.cfg) + ", \"network\": " + ff_hyper(f) +
-		           ", \"n_output_dims\": " + std::to_string(n_output_dims) + ", \"gradient_precision\": \"" + (m->grad_fp16 ? "fp16" : "fp32") + "\"}";
-		module_common_init(m.get(), batch_capacity);
-		*out = m.release();
+		const EncSpec e = enc_from_json(je, n_input_dims, batch_capacity, true);
+		const FfNet f = ff_from_json(jn, e.width(), n_output_dims);
+		auto m = new_module(e, f, jn, batch_capacity);
+		m->enc.layout = ENC_LAYOUT_AOS;
+		if (e.type == EncSpec::Hash16 && f.act == FF_RELU && f.out_act == FF_NONE && f.N == 1 && n_output_dims <= 16 && dnet_supported(e.cfg.n_levels, f.W))
+			m->fused = NeusModule::Dnet;
+		*out = module_finish(std::move(m));
 	});
-}
-
-// A FullyFusedMLP from its config (fully_fused_mlp.cu:816-879): n_neurons 16 / 32 / 64 / 128, n_hidden_layers >= 1, input and
-// output padded to multiples of 16
-static FfNet ff_from_json(const JsonValue& j, uint32_t n_input_dims, uint32_t n_output_dims) {
-	const std::string ot = j.string("otype", "FullyFusedMLP");
-	if (ot != "FullyFusedMLP" && ot != "MegakernelMLP" && ot != "CutlassMLP")
-		throw std::runtime_error("only FullyFusedMLP networks are implemented on gfx950");
-	FfNet f;
-	f.W = (uint32_t)j.number("n_neurons", 64);
-	if (f.W != 16 && f.W != 32 && f.W != 64 && f.W != 128)
-		throw std::runtime_error("FullyFusedMLP only supports 16, 32, 64, and 128 neurons, but got " + std::to_string(f.W));
-	const double nh = j.number("n_hidden_layers", 1);
-	if (nh < 1 || nh > 32) throw std::runtime_error("FullyFusedMLP requires at least 1 hidden layer (3 layers in total).");
-	f.N = (uint32_t)nh;
-	if (n_input_dims == 0 || n_input_dims > 128) throw std::runtime_error("FullyFusedMLP: 1..128 input dims on gfx950");
-	if (n_output_dims == 0 || n_output_dims > 128) throw std::runtime_error("FullyFusedMLP: 1..128 output dims on gfx950");
-	f.n_in = n_input_dims; f.in_pad = (n_input_dims + 15) / 16 * 16;
-	f.n_out = n_output_dims; f.out_pad = (n_output_dims + 15) / 16 * 16;
-	f.act = FfNet::activation(j.string("activation", "ReLU"));
-	f.out_act = FfNet::activation(j.string("output_activation", "None"));
-	f.build();
-	return f;
-}
-static std::string ff_hyper(const FfNet& f) {
-	static const char* an[6] = {"None", "ReLU", "Exponential", "Sigmoid", "Squareplus", "Softplus"};
-	return "{\"otype\": \"FullyFusedMLP\", \"n_neurons\": " + std::to_string(f.W) + ", \"n_hidden_layers\": " + std::to_string(f.N) +
-	       ", \"activation\": \"" + an[f.act] + "\", \"output_activation\": \"" + an[f.out_act] + "\"}";
 }
 
 // tcnn::cpp::create_network(n_input_dims, n_output_dims, network) (cpp_api.cu:170-172): NetworkWithInputEncoding with an
 // Identity encoding (scale 1, offset 0; padded to 16 inputs with ones, identity.h:44-70) and a FullyFusedMLP
-// (fully_fused_mlp.cu:816-879: n_neurons 16 / 32 / 64 / 128, n_hidden_layers >= 1, output padded to 16)
 int neus_module_create_network(uint32_t n_input_dims, uint32_t n_output_dims, const char* network_json, uint32_t batch_capacity, NeusModule** out) {
 	return guard([&] {
 		if (!network_json || !out) throw std::runtime_error("neus_module_create_network: null argument");
-		if (batch_capacity == 0 || batch_capacity % 128 != 0 || batch_capacity > (1u << 24))
-			throw std::runtime_error("batch_capacity must be a positive multiple of 128 (<= 2^24)");
+		check_capacity(batch_capacity);
 		const JsonValue j = parse_json(network_json);
-		*out = make_mlp_module(ff_from_json(j, n_input_dims, n_output_dims), j, batch_capacity);
+		EncSpec e;
+		e.n_in = n_input_dims;
+		auto m = new_module(e, ff_from_json(j, n_input_dims, n_output_dims), j, batch_capacity);
+		*out = module_finish(std::move(m));
 	});
 }
-// NetworkWithInputEncoding(Identity{scale, offset} -> FullyFusedMLP) as a module (create_network, and
-// create_network_with_input_encoding with an Identity encoding)
-static NeusModule* make_mlp_module(const FfNet& f, const JsonValue& j, uint32_t batch_capacity) {
-	{
-		int dev = 0;
-		HIP_CHECK(hipGetDevice(&dev));
-		auto m = std::make_unique<NeusModule>(dev);
-		m->kind = NeusModule::Mlp;
-		module_options(m.get(), j);
-		m->ff = f;
-		m->n_in = f.n_in; m->n_out = f.out_pad;  // cpp::Module::n_output_dims = the padded output width
-		m->capacity = batch_capacity;
-		m->gtmp.alloc(f.P);
-		m->ff_acts.alloc(f.acts_halves(batch_capacity));
-		m->ff_front.alloc((size_t)batch_capacity * (f.in_pad + (size_t)f.N * f.W));
-		const uint32_t dmax = std::max(std::max(f.W, f.out_pad), f.in_pad);
-		m->ff_d[0].alloc((size_t)batch_capacity * dmax); m->ff_d[1].alloc((size_t)batch_capacity * dmax);
-		m->ff_partial.alloc((size_t)ff_wgrad_blocks(batch_capacity) * f.P);
-		m->ff_dummy.alloc(4);
-		m->hyper = "{\"otype\": \"NetworkWithInputEncoding\", \"encoding\": {\"otype\": \"Identity\", \"scale\": " + fmt_float(f.in_scale) +
-		           ", \"offset\": " + fmt_float(f.in_offset) + "}, \"network\": " + ff_hyper(f) + ", \"n_input_dims\": " + std::to_string(f.n_in) +
-		           ", \"n_output_dims\": " + std::to_string(f.n_out) + ", \"gradient_precision\": \"" + (m->grad_fp16 ? "fp16" : "fp32") + "\"}";
-		HIP_CHECK(hipStreamSynchronize(m->core.stream));
-		return m.release();
-	}
-}
-
-namespace {
-// FullyFusedMLP passes (ffmlp.hip). acts: X0 [n][in_pad] then hidden l at n (in_pad + l W), each [n][W].
-const half_t* ff_mat(const FfNet& f, const void* params, uint32_t l) { return (const half_t*)params + f.off[l]; }
-half_t* ff_hidden(const FfNet& f, half_t* acts, uint32_t n, uint32_t l) { return acts + (size_t)n * f.in_pad + (size_t)l * n * f.W; }
-FfLayer ff_layer(const half_t* W, uint32_t O, uint32_t K, bool trans, const half_t* in, uint32_t ldi, uint32_t n) {
-	FfLayer L{};
-	L.W = W; L.O = O; L.K = K; L.trans = trans ? 1u : 0u; L.in = in; L.ldi = ldi; L.n = n;
-	return L;
-}
-// forward (mlp_fused_forward, fully_fused_mlp.cu:678-812): hidden layers act(W x), output out_act(W_N h)
-void ff_forward(const FfNet& f, hipStream_t s, uint32_t n, const float* input, const void* params, half_t* acts, half_t* output) {
-	if (input) launch_ff_input(s, n, f.n_in, f.in_pad, input, f.in_scale, f.in_offset, acts, false);  // (null: X0 already in acts)
-	const half_t* x = acts;
-	uint32_t ldx = f.in_pad;
-	for (uint32_t l = 0; l <= f.N; ++l) {
-		FfLayer L = ff_layer(ff_mat(f, params, l), f.rows[l], f.cols[l], false, x, ldx, n);
-		L.mode = FF_MODE_ACT;
-		L.act = l == f.N ? f.out_act : f.act;
-		L.out = l == f.N ? output : ff_hidden(f, acts, n, l);
-		L.ldo = l == f.N ? f.out_pad : f.W;
-		launch_ff_layer(s, L);
-		x = L.out; ldx = f.W;
-	}
-}
-// delta through layer l (l >= 1) to the input of layer l: act'(h_{l-1}) (W_l^T d)
-void ff_back_through(const FfNet& f, hipStream_t s, uint32_t n, const void* params, uint32_t l, const half_t* d, uint32_t ldd, const half_t* acts_fwd,
-                     half_t* out) {
-	FfLayer L = ff_layer(ff_mat(f, params, l), f.cols[l], f.rows[l], true, d, ldd, n);
-	L.mode = FF_MODE_DACT; L.act = f.act; L.out = out; L.ldo = f.W;
-	L.aux = ff_hidden(f, const_cast<half_t*>(acts_fwd), n, l - 1); L.ldx = f.W;
-	launch_ff_layer(s, L);
-}
-void ff_wgrad(const FfNet& f, hipStream_t s, uint32_t n, uint32_t l, const half_t* d, uint32_t ldd, const half_t* x, uint32_t ldx, float* partial) {
-	FfWgrad G{};
-	G.D = d; G.ldd = ldd; G.O = f.rows[l]; G.X = x; G.ldx = ldx; G.I = f.cols[l];
-	G.partial = partial; G.ld_partial = f.P; G.off = f.off[l]; G.n = n;
-	launch_ff_wgrad(s, G);
-}
-// FullyFusedMLP::backward_impl (fully_fused_mlp.cu:967-1085) of a module's network down to dL/d(its input) as fp16 rows
-// [n][in_pad] (returned; the module's delta ping-pong buffer), with the weight-gradient partials when wgrad
-const half_t* ff_backward_chain(NeusModule* m, hipStream_t s, uint32_t n, const void* params, const half_t* acts, const half_t* dL_doutput,
-                                const half_t* output, bool wgrad) {
-	const FfNet& f = m->ff;
-	const half_t* d = dL_doutput;
-	int pp = 0;
-	if (f.out_act != FF_NONE) { launch_ff_out_delta(s, n, f.out_pad, f.out_act, d, output, m->ff_d[0].p); d = m->ff_d[0].p; pp = 1; }
-	uint32_t ldd = f.out_pad;
-	for (uint32_t l = f.N + 1; l-- > 0;) {
-		const half_t* x = l == 0 ? acts : ff_hidden(f, const_cast<half_t*>(acts), n, l - 1);
-		if (wgrad) ff_wgrad(f, s, n, l, d, ldd, x, l == 0 ? f.in_pad : f.W, m->ff_partial.p);
-		if (l > 0) {
-			ff_back_through(f, s, n, params, l, d, ldd, acts, m->ff_d[pp].p);
-			d = m->ff_d[pp].p; pp ^= 1; ldd = f.W;
-		} else {
-			FfLayer L = ff_layer(ff_mat(f, params, 0), f.in_pad, f.W, true, d, ldd, n);
-			L.mode = FF_MODE_ACT; L.act = FF_NONE; L.out = m->ff_d[pp].p; L.ldo = f.in_pad;
-			launch_ff_layer(s, L);
-			d = m->ff_d[pp].p;
-		}
-	}
-	return d;
-}
-// FullyFusedMLP::backward_backward_input_impl (fully_fused_mlp.cu:1088-1198) with the front f_0 = the network's
-// dL_ddLdinput already in m->ff_front as rows [n][in_pad]: fronts f_i = act'(h_{i-1}) (W_{i-1} f_{i-1}); dL_ddLdoutput (when
-// asked for) = the front carried through the output matrix, f_{N+1} = W_N f_N, as [n][out_pad] fp16; with wgrad the backs
-// b_{N+2} = dL_doutput, b_i = act'(h_{i-2}) (W_{i-1}^T b_{i+1}) and dW_{i-1} = b_{i+1} f_{i-1}^T into the partials
-void ff_bbi_chain(NeusModule* m, hipStream_t s, uint32_t n, const void* params, const half_t* acts, const half_t* dL_doutput, bool wgrad,
-                  half_t* dL_ddLdoutput) {
-	const FfNet& f = m->ff;
-	half_t* fr = m->ff_front.p;
-	auto front = [&](uint32_t i) { return i == 0 ? fr : fr + (size_t)n * f.in_pad + (size_t)(i - 1) * n * f.W; };
-	for (uint32_t i = 1; i <= f.N; ++i) {
-		FfLayer L = ff_layer(ff_mat(f, params, i - 1), f.rows[i - 1], f.cols[i - 1], false, front(i - 1), i == 1 ? f.in_pad : f.W, n);
-		L.mode = FF_MODE_DACT; L.act = f.act; L.out = front(i); L.ldo = f.W;
-		L.aux = ff_hidden(f, const_cast<half_t*>(acts), n, i - 1); L.ldx = f.W;
-		launch_ff_layer(s, L);
-	}
-	if (dL_ddLdoutput) {
-		FfLayer L = ff_layer(ff_mat(f, params, f.N), f.rows[f.N], f.cols[f.N], false, front(f.N), f.W, n);
-		L.mode = FF_MODE_ACT; L.act = FF_NONE; L.out = dL_ddLdoutput; L.ldo = f.out_pad;
-		launch_ff_layer(s, L);
-	}
-	if (!wgrad) return;
-	const half_t* b = dL_doutput;
-	uint32_t ldb = f.out_pad;
-	int pp = 0;
-	for (uint32_t l = f.N + 1; l-- > 0;) {
-		ff_wgrad(f, s, n, l, b, ldb, front(l), l == 0 ? f.in_pad : f.W, m->ff_partial.p);
-		if (l > 0) {
-			ff_back_through(f, s, n, params, l, b, ldb, acts, m->ff_d[pp].p);
-			b = m->ff_d[pp].p; pp ^= 1; ldb = f.W;
-		}
-	}
-}
-}  // namespace
 
 int neus_module_destroy(NeusModule* m) { return guard([&] { delete m; }); }
 int neus_context_destroy(NeusContext* c) { return guard([&] { delete c; }); }
@@ -3928,19 +4046,15 @@ int neus_context_destroy(NeusContext* c) { return guard([&] { delete c; }); }
 int neus_module_info(const NeusModule* m, NeusModuleInfo* o) {
 	return guard([&] {
 		if (!m || !o) throw std::runtime_error("neus_module_info: null argument");
-		o->n_params = m->n_params();
+		o->n_params = m->P;
 		o->n_input_dims = m->n_in;
 		o->n_output_dims = m->n_out;
-		o->param_precision = m->f32 ? NEUS_PRECISION_FP32 : NEUS_PRECISION_FP16;
-		o->output_precision = m->f32 ? NEUS_PRECISION_FP32 : NEUS_PRECISION_FP16;
+		o->param_precision = m->enc.f32 ? NEUS_PRECISION_FP32 : NEUS_PRECISION_FP16;
+		o->output_precision = m->enc.f32 ? NEUS_PRECISION_FP32 : NEUS_PRECISION_FP16;
 		o->gradient_precision = NEUS_PRECISION_FP32;
 		o->batch_capacity = m->capacity;
-		o->n_levels = m->core.lay.L;
-		o->grid_offset = m->kind == NeusModule::Network ? m->core.lay.grid_off : (m->kind == NeusModule::DensityNet ? m->n_mlp : 0);
-		if (m->kind == NeusModule::Mlp || m->kind == NeusModule::EncMlp || m->kind == NeusModule::PfEncoding) {  // no encoding parameters
-			o->n_levels = 0; o->grid_offset = (uint32_t)m->n_params();
-		}
-		if (m->kind == NeusModule::GridMlp || m->kind == NeusModule::NdGridMlp) o->grid_offset = m->ff.P;
+		o->n_levels = m->enc.n_params() ? m->core.lay.L : 0;
+		o->grid_offset = m->enc_off;
 		o->per_level_scale = m->core.cfg.per_level_scale;
 	});
 }
@@ -3953,49 +4067,32 @@ int neus_module_hyperparams(const NeusModule* m, char* buf, uint64_t cap, uint64
 	});
 }
 
-int neus_module_set_training_step(NeusModule* m, int training_step) { return guard([&] { m->training_step = training_step; }); }
+int neus_module_set_training_step(NeusModule* m, int training_step) { return guard([&] { m->enc.training_step = training_step; }); }
 int neus_module_set_indeed_batch_size(NeusModule* m, uint32_t n) { return guard([&] { m->indeed_batch = n; }); }
 
 int neus_module_initialize_params(NeusModule* m, uint64_t seed, float* params_full_precision) {
 	return guard([&] {
-		if (!m || (!params_full_precision && m->n_params())) throw std::runtime_error("neus_module_initialize_params: null argument");
-		if (m->n_params() == 0) return;  // a parameter-free encoding
+		if (!m || (!params_full_precision && m->P)) throw std::runtime_error("neus_module_initialize_params: null argument");
+		if (m->P == 0) return;  // a parameter-free encoding
 		HIP_CHECK(hipSetDevice(m->core.device));
 		std::vector<float> h;
 		// cpp::Module::initialize_params draws from pcg32{seed} (cpp_api.cu:162-165; the Trainer's seed_seq is not involved)
-		if (m->kind == NeusModule::Mlp || m->kind == NeusModule::EncMlp) {
-			// NetworkWithInputEncoding::initialize_params: Identity (and every other parameter-free encoding) has none; FullyFusedMLP::initialize_params
-			// (fully_fused_mlp.cu:1229-1256): every matrix xavier-uniform in order, U(+-sqrt(6 / (fan_in + fan_out)))
-			// (gpu_matrix.h:292-306) from pcg32{seed} (cpp_api.cu:162-165)
-			h.assign(m->ff.P, 0.f);
-			pcg32 rnd = make_pcg32(seed);
-			for (uint32_t l = 0; l <= m->ff.N; ++l) {
-				const float scale = std::sqrt(6.0f / (float)(m->ff.rows[l] + m->ff.cols[l]));
-				for (uint32_t i = 0; i < m->ff.rows[l] * m->ff.cols[l]; ++i) h[m->ff.off[l] + i] = rnd.next_float() * 2.0f * scale - scale;
-			}
-		} else if (m->kind == NeusModule::Network) {
+		if (m->fused == NeusModule::Nerf) {
 			h = m->core.initial_params_rng(make_pcg32(seed), nullptr);
-		} else {  // [FullyFusedMLP xavier matrices (fully_fused_mlp.cu:1229-1256)] then GridEncoding::initialize_params:
-			      // generate_random_uniform(rnd, n_params, -1e-4, 1e-4) (grid.h:2375-2380)
-			h.assign(m->n_params(), 0.f);
+		} else {
+			// NetworkWithInputEncoding::initialize_params: the network, then the encoding. FullyFusedMLP::initialize_params
+			// (fully_fused_mlp.cu:1229-1256): every matrix xavier-uniform in order, U(+-sqrt(6 / (fan_in + fan_out)))
+			// (gpu_matrix.h:292-306); GridEncoding::initialize_params: generate_random_uniform(rnd, n_params, -1e-4, 1e-4)
+			// (grid.h:2375-2380); the parameter-free encodings have none
+			h.assign(m->P, 0.f);
 			pcg32 rnd = make_pcg32(seed);
 			size_t off = 0;
-			if (m->kind == NeusModule::GridMlp || m->kind == NeusModule::NdGridMlp) {  // NetworkWithInputEncoding::initialize_params: the network, then the encoding
-				for (uint32_t l = 0; l <= m->ff.N; ++l) {
-					const float scale = std::sqrt(6.0f / (float)(m->ff.rows[l] + m->ff.cols[l]));
-					for (uint32_t i = 0; i < m->ff.rows[l] * m->ff.cols[l]; ++i) h[off + i] = rnd.next_float() * 2.0f * scale - scale;
-					off += (size_t)m->ff.rows[l] * m->ff.cols[l];
-				}
-			}
-			if (m->kind == NeusModule::DensityNet) {
-				auto xavier = [&](uint32_t out, uint32_t in) {
-					const float scale = std::sqrt(6.0f / (float)(in + out));
-					for (uint32_t i = 0; i < out * in; ++i) h[off + i] = rnd.next_float() * 2.0f * scale - scale;
-					off += (size_t)out * in;
-				};
-				xavier(m->dn_width, m->dn_de);
-				xavier(16, m->dn_width);
-			}
+			auto xavier = [&](uint32_t out, uint32_t in) {
+				const float scale = std::sqrt(6.0f / (float)(in + out));
+				for (uint32_t i = 0; i < out * in; ++i) h[off + i] = rnd.next_float() * 2.0f * scale - scale;
+				off += (size_t)out * in;
+			};
+			for (size_t l = 0; l < m->ff.rows.size(); ++l) xavier(m->ff.rows[l], m->ff.cols[l]);
 			float* hg = h.data() + off;
 			const size_t N = h.size() - off, per = 4, n_threads = (N + per - 1) / per, n_pad = (n_threads + 127) / 128 * 128;
 			for (size_t i = 0; i < n_pad; ++i) {
@@ -4011,544 +4108,208 @@ int neus_module_initialize_params(NeusModule* m, uint64_t seed, float* params_fu
 	});
 }
 
-static void module_forward(NeusModule* m, hipStream_t s, uint32_t n, const float* input, void* output, const void* params, NeusContext* ctx) {
-	if (!input || !output) throw std::runtime_error("module forward: null input / output");
-	m->check_n(n, false);
+// ---------------------------------------------------------------- the two fused specials
+namespace {
+// the NeuS NerfNetwork: params into the core's fp16 buffer and its transposed weight copies, then the Testbed's kernels
+void nerf_load_params(NeusModule* m, const void* params, hipStream_t s) {
+	if (!params) throw std::runtime_error("module: null params");
+	HIP_CHECK(hipMemcpyAsync(m->core.params_h.p, params, (size_t)m->core.lay.P * 2, hipMemcpyDeviceToDevice, s));
+	m->core.prepare_weights();
+}
+void nerf_forward(NeusModule* m, hipStream_t s, uint32_t n, const float* input, void* output, const void* params) {
+	nerf_load_params(m, params, s);
+	m->core.net_forward(nullptr, n, n, input, m->enc.valid(), (half_t*)output, s);
+}
+// NerfNetwork::backward (nerf_network.h:330-601): first and second order in one pass; the Testbed's forward-recompute +
+// backward writes every parameter gradient (Overwrite) into g
+void nerf_backward(NeusModule* m, hipStream_t s, uint32_t n, const float* input, const void* dL_doutput, const void* params, float* g, float* dL_dinput) {
 	NeusTestbed& t = m->core;
-	if (m->kind == NeusModule::Mlp) {
-		if (!params) throw std::runtime_error("module: null params");
-		if (ctx) ctx->acts.alloc(std::max<size_t>(1, m->ff.acts_halves(n)));
-		ff_forward(m->ff, s, n, input, params, ctx ? ctx->acts.p : m->ff_acts.p, (half_t*)output);
-		HIP_CHECK(hipGetLastError());
-		return;
+	nerf_load_params(m, params, s);
+	float* gg = g ? g : m->gtmp.p;
+	HIP_CHECK(hipMemsetAsync(gg, 0, (size_t)t.lay.P * 4, s));
+	const float saved = t.tbuf.indeed_batch;
+	t.tbuf.indeed_batch = (float)(m->indeed_batch ? m->indeed_batch : n);
+	t.tbuf.dpos = dL_dinput ? m->dpos.p : nullptr;
+	t.net_backward(nullptr, nullptr, n, input, m->enc.valid(), (const half_t*)dL_doutput, gg, s);
+	t.tbuf.dpos = nullptr;
+	t.tbuf.indeed_batch = saved;
+	if (dL_dinput) {  // position columns; dt and direction columns are 0 (the direction gradient is not propagated)
+		HIP_CHECK(hipMemset2DAsync(dL_dinput, COORD_W * 4, 0, COORD_W * 4, n, s));
+		HIP_CHECK(hipMemcpy2DAsync(dL_dinput, COORD_W * 4, m->dpos.p, 16, 12, n, hipMemcpyDeviceToDevice, s));
 	}
-	if (m->kind == NeusModule::PfEncoding) {
-		launch_pf_out(s, m->pf, n, input, nullptr, m->pf_view(output, n));
-		HIP_CHECK(hipGetLastError());
-		return;
+}
+
+// k_dnet: the HashGrid's paired encoding straight into one fused kernel per pass; the encoding's steps are Enc's
+DNetLaunch dnet_args(const NeusModule* m, const void* params, const uint32_t* enc) {
+	DNetLaunch d{};
+	d.w0 = (const half_t*)params; d.w1 = d.w0 + (size_t)m->ff.W * m->ff.in_pad; d.enc = enc;
+	return d;
+}
+// NetworkWithInputEncoding::forward (network_with_input_encoding.h:84-111): encoding, then the MLP on it
+void dnet_forward(NeusModule* m, hipStream_t s, uint32_t n, const float* input, void* output, const void* params, NeusContext* ctx) {
+	uint32_t* enc = m->enc.paired_out(ctx, n);
+	m->enc.hash_encode(s, n, input, (const half_t*)m->enc_params(params), ctx, enc);
+	DNetLaunch d = dnet_args(m, params, enc);
+	d.out = (half_t*)output;
+	launch_dnet(s, m->enc.L(), m->ff.W, 0, n, d);
+}
+// NetworkWithInputEncoding::backward (network_with_input_encoding.h:113-156): the MLP backward gives its weight gradients
+// and dL/d(encoding); the encoding's backward the grid gradients and dL_dinput
+void dnet_backward(NeusModule* m, hipStream_t s, uint32_t n, const NeusContext* ctx, const float* input, const void* dL_doutput, const void* params,
+                   float* g, float* dL_dinput) {
+	Enc& e = m->enc;
+	if (!params) throw std::runtime_error("module: null params");
+	if (!m->ctx_ok(ctx)) throw std::runtime_error("module backward: the context is not from this module's forward");
+	DNetLaunch d = dnet_args(m, params, ctx->enc.p);
+	d.dL = (const half_t*)dL_doutput; d.denc = e.denc_tmp.p; d.wpartial = m->fw.partial.p;
+	launch_dnet(s, e.L(), m->ff.W, 1, n, d);
+	const half_t* denc = (const half_t*)e.denc_tmp.p;
+	if (g) {
+		ff_reduce(m->ff, m->fw, s, dnet_blocks(n), g);
+		e.hash_scatter(s, n, input, denc, e.zero_h.p, e.zero_v.p, g + m->enc_off);
 	}
-	if (m->kind == NeusModule::EncMlp) {
-		// NetworkWithInputEncoding::forward: the encoding straight into the FullyFusedMLP's fp16 input rows (padded to 16 with
-		// ones, as tcnn's encodings pad), then the layers
-		if (!params) throw std::runtime_error("module: null params");
-		half_t* acts = m->ff_acts.p;
-		if (ctx) { ctx->acts.alloc(std::max<size_t>(1, m->ff.acts_halves(n))); acts = ctx->acts.p; }
-		launch_pf_rows(s, m->pf, n, input, nullptr, acts, m->ff.in_pad);
-		ff_forward(m->ff, s, n, nullptr, params, acts, (half_t*)output);
-		HIP_CHECK(hipGetLastError());
-		return;
+	if (dL_dinput) launch_enc_input_grad(s, n, n, e.L(), denc, ctx->dydx.p, dL_dinput, 3);
+}
+// NetworkWithInputEncoding::backward_backward_input (network_with_input_encoding.h:159-250): u = dy/dx . dL_ddLdinput
+// (kernel_grid_backward_input_backward_dLdoutput), the MLP's backward-backward (fully_fused_mlp.cu:1088-1198: b2 =
+// relu'(H0) W1^T dL, h1' = relu'(H0) W0 u; dW0 = b2 u^T, dW1 = dL h1'^T) and the encoding's second-order grid
+// gradient with dL/d(encoding) = W0^T b2. dL_ddLdoutput = W1 h1' (one more MFMA of the fused kernel); dL_dinput = the
+// HashGrid's second derivative in x (k_grid_ddx) with dL/d(encoding) as its dL_doutput.
+void dnet_bbi(NeusModule* m, hipStream_t s, uint32_t n, const NeusContext* ctx, const float* input, const float* u, const void* dL_doutput,
+              const void* params, float* g, void* dL_ddLdoutput, float* dL_dinput) {
+	Enc& e = m->enc;
+	launch_enc_ddLdoutput(s, n, n, e.L(), u, ctx->dydx.p, (half_t*)e.u_tmp.p, e.v4.p);
+	DNetLaunch d = dnet_args(m, params, ctx->enc.p);
+	d.dL = (const half_t*)dL_doutput; d.u = e.u_tmp.p; d.denc = e.denc_tmp.p; d.wpartial = m->fw.partial.p; d.out = (half_t*)dL_ddLdoutput;
+	launch_dnet(s, e.L(), m->ff.W, 2, n, d);
+	const half_t* denc = (const half_t*)e.denc_tmp.p;
+	if (g) {
+		ff_reduce(m->ff, m->fw, s, dnet_blocks(n), g);
+		e.hash_scatter(s, n, input, e.zero_h.p, denc, e.v4.p, g + m->enc_off);
 	}
-	if (m->kind == NeusModule::NdGrid) {
-		if (!params) throw std::runtime_error("module: null params");
-		launch_grid_nd_forward(s, n, m->nd, m->valid(), input, params, m->f32, m->nd_view(output, n), 0);
-		HIP_CHECK(hipGetLastError());
-		return;
-	}
-	if (m->kind == NeusModule::NdGridMlp) {
-		// the general grid straight into the FullyFusedMLP's fp16 input rows (padding columns zero, grid.h:1540-1550), then the layers
-		if (!params) throw std::runtime_error("module: null params");
+	if (dL_dinput) e.hash_ddx(s, n, input, (const half_t*)m->enc_params(params), denc, u, dL_dinput);
+}
+}  // namespace
+
+// ---------------------------------------------------------------- the calls
+// NetworkWithInputEncoding::forward (network_with_input_encoding.h:113-124): the encoding, straight into the FullyFusedMLP's
+// fp16 input rows where there is a network, then its layers
+static void module_forward(NeusModule* m, void* stream, uint32_t n, const float* input, void* output, const void* params, NeusContext* ctx) {
+	if (!input || !output) throw std::runtime_error("module forward: null input / output");
+	if (!params && m->P) throw std::runtime_error("module: null params");
+	m->check_n(n, false);
+	HIP_CHECK(hipSetDevice(m->core.device));
+	StreamSwap sw(m->core, stream);
+	hipStream_t s = m->core.stream;
+	if (m->fused == NeusModule::Nerf) nerf_forward(m, s, n, input, output, params);
+	else if (m->fused == NeusModule::Dnet) dnet_forward(m, s, n, input, output, params, ctx);
+	else {
 		const FfNet& f = m->ff;
-		half_t* acts = m->ff_acts.p;
-		if (ctx) { ctx->acts.alloc(std::max<size_t>(1, f.acts_halves(n))); acts = ctx->acts.p; }
-		launch_grid_nd_forward(s, n, m->nd, m->valid(), input, (const half_t*)params + f.P, false, m->nd_rows(acts), f.in_pad - m->n_out_nd());
-		ff_forward(f, s, n, nullptr, params, acts, (half_t*)output);
-		HIP_CHECK(hipGetLastError());
-		return;
-	}
-	if (m->kind == NeusModule::GridMlp) {
-		// NetworkWithInputEncoding::forward (network_with_input_encoding.h:113-124): the HashGrid (zero-padded to the MLP's
-		// input width, grid.h:1540-1550), then the FullyFusedMLP on it
-		if (!params) throw std::runtime_error("module: null params");
-		const FfNet& f = m->ff;
-		uint32_t* enc = m->enc_tmp.p;
-		float* dydx = nullptr;
-		half_t* acts = m->ff_acts.p;
-		if (ctx) {
-			ctx->dydx.alloc((size_t)6 * t.lay.L * std::max(1u, n)); dydx = ctx->dydx.p;
-			ctx->enc.alloc((size_t)t.lay.L * std::max(1u, n)); enc = ctx->enc.p;
-			ctx->acts.alloc(std::max<size_t>(1, f.acts_halves(n))); acts = ctx->acts.p;
-		}
-		const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((n + 255) / 256, 4096));
-		launch_grid_encode(s, nullptr, n, n, input, 3, t.gl, m->valid(), (const half_t*)params + f.P, enc, dydx, gx);
-		launch_enc_to_rows(s, n, t.lay.L, enc, acts, f.in_pad);
-		ff_forward(f, s, n, nullptr, params, acts, (half_t*)output);
-		HIP_CHECK(hipGetLastError());
-		return;
-	}
-	if (m->kind == NeusModule::DensityNet) {
-		// NetworkWithInputEncoding::forward (network_with_input_encoding.h:84-111): encoding, then the MLP on it
-		if (!params) throw std::runtime_error("module: null params");
-		const half_t* ph = (const half_t*)params;
-		float* dydx = nullptr;
-		uint32_t* enc = m->enc_tmp.p;
-		if (ctx) {
-			ctx->dydx.alloc((size_t)6 * t.lay.L * std::max(1u, n)); dydx = ctx->dydx.p;
-			ctx->enc.alloc((size_t)t.lay.L * std::max(1u, n)); enc = ctx->enc.p;
-		}
-		const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((n + 255) / 256, 4096));
-		launch_grid_encode(s, nullptr, n, n, input, 3, t.gl, m->valid(), ph + m->n_mlp, enc, dydx, gx);
-		DNetLaunch d{};
-		d.w0 = ph; d.w1 = ph + (size_t)m->dn_width * m->dn_de; d.enc = enc; d.out = (half_t*)output;
-		launch_dnet(s, t.lay.L, m->dn_width, 0, n, d);
-		HIP_CHECK(hipGetLastError());
-		return;
-	}
-	if (m->f32) {  // GridEncoding<float>::forward (kernel_grid with T = float)
-		if (!params) throw std::runtime_error("module: null params");
-		float* dydx = nullptr;
-		if (ctx) { ctx->dydx.alloc((size_t)6 * t.lay.L * std::max(1u, n)); dydx = ctx->dydx.p; }
-		launch_grid_f32_forward(s, n, t.gl, m->valid(), input, (const float*)params, (float*)output, m->layout, dydx);
-		HIP_CHECK(hipGetLastError());
-		return;
-	}
-	m->load_params(params, s);
-	if (m->kind == NeusModule::Network) {
-		t.net_forward(nullptr, n, n, input, m->valid(), (half_t*)output, s);
-	} else {
-		float* dydx = nullptr;
-		if (ctx) { ctx->dydx.alloc((size_t)6 * t.lay.L * std::max(1u, n)); dydx = ctx->dydx.p; }
-		const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((n + 255) / 256, 4096));
-		uint32_t* enc = m->layout == ENC_LAYOUT_PAIRED ? (uint32_t*)output : m->enc_tmp.p;
-		launch_grid_encode(s, nullptr, n, n, input, 3, t.gl, m->valid(), t.params_h.p + t.lay.grid_off, enc, dydx, gx);
-		if (m->layout != ENC_LAYOUT_PAIRED) launch_enc_to_layout(s, n, t.lay.L, enc, (half_t*)output, m->layout);
+		const bool net = m->net();
+		half_t* acts = m->fw.acts.p;
+		if (net && ctx) { ctx->acts.alloc(std::max<size_t>(1, f.acts_halves(n))); acts = ctx->acts.p; }
+		m->enc.encode(s, n, input, m->enc_params(params), ctx, net ? enc_io(acts, f.in_pad) : enc_io(output, 0));
+		if (net) ff_forward(f, s, n, params, acts, (half_t*)output);
 	}
 	HIP_CHECK(hipGetLastError());
 }
 
 int neus_module_inference(NeusModule* m, void* stream, uint32_t n, const float* input, void* output, const void* params) {
-	return guard([&] {
-		HIP_CHECK(hipSetDevice(m->core.device));
-		StreamSwap sw(m->core, stream);
-		module_forward(m, m->core.stream, n, input, output, params, nullptr);
-	});
+	return guard([&] { module_forward(m, stream, n, input, output, params, nullptr); });
 }
 
 int neus_module_forward(NeusModule* m, void* stream, uint32_t n, const float* input, void* output, const void* params,
                         int prepare_input_gradients, NeusContext** ctx_out) {
 	return guard([&] {
 		if (!ctx_out) throw std::runtime_error("neus_module_forward: null context output");
-		HIP_CHECK(hipSetDevice(m->core.device));
-		StreamSwap sw(m->core, stream);
 		auto ctx = std::make_unique<NeusContext>();
 		ctx->n = n;
-		// the NerfNetwork's backward recomputes its forward; the encodings keep dy/dx for dL_dinput and second order
+		// the NerfNetwork's backward recomputes its forward; the HashGrid keeps dy/dx for dL_dinput and second order, the
+		// network its activations
 		(void)prepare_input_gradients;
-		module_forward(m, m->core.stream, n, input, output, params, m->kind != NeusModule::Network ? ctx.get() : nullptr);
+		module_forward(m, stream, n, input, output, params, ctx.get());
 		*ctx_out = ctx.release();
 	});
 }
 
+// NetworkWithInputEncoding::backward (network_with_input_encoding.h:126-156): the FullyFusedMLP's backward (weight
+// gradients, dL/dX0 as fp16 rows), then the encoding's backward of that (its parameter gradient, dL_dinput)
 int neus_module_backward(NeusModule* m, void* stream, const NeusContext* ctx, uint32_t n, float* dL_dinput, const void* dL_doutput,
                          void* dL_dparams, const float* input, const void* output, const void* params, int gradient_mode) {
 	return guard([&] {
-		(void)output;
 		if (!ctx || ctx->n != n) throw std::runtime_error("module backward: the context is not from a forward over n_elements");
 		if (!input || !dL_doutput) throw std::runtime_error("module backward: null input / dL_doutput");
 		m->check_n(n, true);
 		HIP_CHECK(hipSetDevice(m->core.device));
 		StreamSwap sw(m->core, stream);
-		NeusTestbed& t = m->core;
-		hipStream_t s = t.stream;
-		float* g = m->n_params() ? m->grad_target(dL_dparams, gradient_mode) : nullptr;
+		hipStream_t s = m->core.stream;
+		float* g = m->grad_target(dL_dparams, gradient_mode);
 		if (!g && !dL_dinput) return;
-		if (m->kind == NeusModule::PfEncoding) {  // dL_dinput = J^T dL_doutput, the Jacobian recomputed from the input
-			launch_pf_input_grad(s, m->pf, n, input, m->pf_view(dL_doutput, n), nullptr, dL_dinput);
-			HIP_CHECK(hipGetLastError());
-			return;
-		}
-		if (m->kind == NeusModule::EncMlp) {
-			// NetworkWithInputEncoding::backward: the FullyFusedMLP's backward (weight gradients, dL/dX0 as fp16 rows), then the
-			// encoding's J^T on it
+		if (m->fused == NeusModule::Nerf) nerf_backward(m, s, n, input, dL_doutput, params, g, dL_dinput);
+		else if (m->fused == NeusModule::Dnet) dnet_backward(m, s, n, ctx, input, dL_doutput, params, g, dL_dinput);
+		else {
 			const FfNet& f = m->ff;
-			if (!params) throw std::runtime_error("module: null params");
-			if (!ctx->acts.p) throw std::runtime_error("module backward: the context is not from this module's forward");
-			if (f.out_act != FF_NONE && !output) throw std::runtime_error("FullyFusedMLP backward: the forward output is needed for its output activation");
-			const half_t* dX0 = ff_backward_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, (const half_t*)output, g != nullptr);
-			if (dL_dinput) launch_pf_input_grad(s, m->pf, n, input, PfView{const_cast<half_t*>(dX0), f.in_pad, 1, 0u}, nullptr, dL_dinput);
-			if (g) {
-				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
-				m->finish_grad(dL_dparams, gradient_mode, s);
+			const bool net = m->net();
+			if (net) {
+				if (!params) throw std::runtime_error("module: null params");
+				if (!ctx->acts.p) throw std::runtime_error("module backward: the context is not from this module's forward");
+				if (f.out_act != FF_NONE && !output) throw std::runtime_error("FullyFusedMLP backward: the forward output is needed for its output activation");
 			}
-			HIP_CHECK(hipGetLastError());
-			return;
+			m->enc.check_backward(ctx, params, dL_dinput, !net);
+			EncIO dy = enc_io(dL_doutput, 0);
+			if (net)
+				dy = enc_io(ff_backward_chain(f, m->fw, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, (const half_t*)output, g != nullptr,
+				                              m->enc.sink(dL_dinput)), f.in_pad);
+			m->enc.backward(s, n, ctx, input, dy, m->enc_params(params), g && m->enc.n_params() ? g + m->enc_off : nullptr, dL_dinput);
 		}
-		if (m->kind == NeusModule::Mlp) {
-			// FullyFusedMLP::backward_impl (fully_fused_mlp.cu:967-1085): the output activation's backward on dL/doutput, the
-			// deltas through the hidden layers (activation derivative from the stored outputs), dW = D^T x per layer and
-			// dL/dinput = W_0^T D_0 through the Identity encoding's backward (identity.h:86-104: x scale = 1)
-			const FfNet& f = m->ff;
-			if (!params) throw std::runtime_error("module: null params");
-			if (!ctx->acts.p) throw std::runtime_error("module backward: the context is not from this module's forward");
-			if (f.out_act != FF_NONE && !output) throw std::runtime_error("FullyFusedMLP backward: the forward output is needed for its output activation");
-			const half_t* d = (const half_t*)dL_doutput;
-			int pp = 0;
-			if (f.out_act != FF_NONE) { launch_ff_out_delta(s, n, f.out_pad, f.out_act, d, (const half_t*)output, m->ff_d[0].p); d = m->ff_d[0].p; pp = 1; }
-			uint32_t ldd = f.out_pad;
-			for (uint32_t l = f.N + 1; l-- > 0;) {
-				const half_t* x = l == 0 ? ctx->acts.p : ff_hidden(f, ctx->acts.p, n, l - 1);
-				if (g) ff_wgrad(f, s, n, l, d, ldd, x, l == 0 ? f.in_pad : f.W, m->ff_partial.p);
-				if (l > 0) {
-					ff_back_through(f, s, n, params, l, d, ldd, ctx->acts.p, m->ff_d[pp].p);
-					d = m->ff_d[pp].p; pp ^= 1; ldd = f.W;
-				} else if (dL_dinput) {
-					FfLayer L = ff_layer(ff_mat(f, params, 0), f.in_pad, f.W, true, d, ldd, n);
-					L.mode = FF_MODE_F32; L.out_f = dL_dinput; L.ldo = f.n_in; L.o_lim = f.n_in; L.out_scale = f.in_scale;
-					launch_ff_layer(s, L);
-				}
-			}
-			if (g) {
-				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
-				m->finish_grad(dL_dparams, gradient_mode, s);
-			}
-			HIP_CHECK(hipGetLastError());
-			return;
-		}
-		const uint32_t valid = m->valid();
-		if (m->kind == NeusModule::NdGrid) {
-			// kernel_grid_backward by fp32 atomics into a zeroed buffer; dL_dinput with the Jacobian gathered again from the input
-			if (dL_dinput && !params) throw std::runtime_error("module: null params");
-			if (g) {
-				HIP_CHECK(hipMemsetAsync(g, 0, (size_t)m->n_params() * 4, s));
-				launch_grid_nd_backward(s, n, m->nd, valid, input, m->nd_view(dL_doutput, n), g);
-			}
-			if (dL_dinput) launch_grid_nd_input_grad(s, n, m->nd, valid, input, params, m->f32, m->nd_view(dL_doutput, n), m->nd_scratch(), dL_dinput);
-			if (g) m->finish_grad(dL_dparams, gradient_mode, s);
-			HIP_CHECK(hipGetLastError());
-			return;
-		}
-		if (m->kind == NeusModule::NdGridMlp) {
-			// NetworkWithInputEncoding::backward (network_with_input_encoding.h:126-156): the FullyFusedMLP's backward (weight
-			// gradients, dL/dX0 as fp16 rows), then the grid's two gradients of it
-			const FfNet& f = m->ff;
-			if (!params) throw std::runtime_error("module: null params");
-			if (!ctx->acts.p) throw std::runtime_error("module backward: the context is not from this module's forward");
-			if (f.out_act != FF_NONE && !output) throw std::runtime_error("FullyFusedMLP backward: the forward output is needed for its output activation");
-			const half_t* dX0 = ff_backward_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, (const half_t*)output, g != nullptr);
-			if (g) {
-				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
-				HIP_CHECK(hipMemsetAsync(g + f.P, 0, (size_t)(m->n_params() - f.P) * 4, s));
-				launch_grid_nd_backward(s, n, m->nd, valid, input, m->nd_rows(dX0), g + f.P);
-			}
-			if (dL_dinput)
-				launch_grid_nd_input_grad(s, n, m->nd, valid, input, (const half_t*)params + f.P, false, m->nd_rows(dX0), m->nd_scratch(), dL_dinput);
-			if (g) m->finish_grad(dL_dparams, gradient_mode, s);
-			HIP_CHECK(hipGetLastError());
-			return;
-		}
-		if (m->kind == NeusModule::GridMlp) {
-			// NetworkWithInputEncoding::backward (network_with_input_encoding.h:126-156): the FullyFusedMLP's backward (weight
-			// gradients, dL/d(its input) in fp16) and the HashGrid's backward of that (grid gradients, dL_dinput from dy/dx)
-			const FfNet& f = m->ff;
-			if (!params) throw std::runtime_error("module: null params");
-			if (!ctx->acts.p || !ctx->dydx.p) throw std::runtime_error("module backward: the context is not from this module's forward");
-			if (f.out_act != FF_NONE && !output) throw std::runtime_error("FullyFusedMLP backward: the forward output is needed for its output activation");
-			const half_t* dX0 = ff_backward_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, (const half_t*)output, g != nullptr);
-			launch_enc_from_rows(s, n, t.lay.L, dX0, f.in_pad, m->denc_tmp.p);
-			if (g) {
-				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
-				launch_grid_scatter(s, nullptr, n, n, input, 3, t.gl, valid, (const half_t*)m->denc_tmp.p, m->zero_h.p, m->zero_v.p, g + f.P,
-				                    t.swork, t.scan_tmp.p, t.scan_tmp_bytes);
-			}
-			if (dL_dinput) launch_enc_input_grad(s, n, n, t.lay.L, (const half_t*)m->denc_tmp.p, ctx->dydx.p, dL_dinput, 3);
-			if (g) m->finish_grad(dL_dparams, gradient_mode, s);
-			HIP_CHECK(hipGetLastError());
-			return;
-		}
-		if (m->kind == NeusModule::DensityNet) {
-			// NetworkWithInputEncoding::backward (network_with_input_encoding.h:113-156): the MLP backward gives its weight
-			// gradients and dL/d(encoding); the encoding's backward the grid gradients and dL_dinput
-			if (!params) throw std::runtime_error("module: null params");
-			if (!ctx->enc.p || !ctx->dydx.p) throw std::runtime_error("module backward: the context is not from this module's forward");
-			const half_t* ph = (const half_t*)params;
-			DNetLaunch d{};
-			d.w0 = ph; d.w1 = ph + (size_t)m->dn_width * m->dn_de; d.enc = ctx->enc.p; d.dL = (const half_t*)dL_doutput;
-			d.denc = m->denc_tmp.p; d.wpartial = m->dn_partial.p;
-			launch_dnet(s, t.lay.L, m->dn_width, 1, n, d);
-			if (g) {
-				launch_mlp_grad_reduce(s, MlpGradReduce{m->dn_partial.p, dnet_blocks(n), m->n_mlp, g, nullptr, nullptr, 0, m->dn_dummy.p});
-				launch_grid_scatter(s, nullptr, n, n, input, 3, t.gl, valid, (const half_t*)m->denc_tmp.p, m->zero_h.p, m->zero_v.p, g + m->n_mlp,
-				                    t.swork, t.scan_tmp.p, t.scan_tmp_bytes);
-			}
-			if (dL_dinput) launch_enc_input_grad(s, n, n, t.lay.L, (const half_t*)m->denc_tmp.p, ctx->dydx.p, dL_dinput, 3);
-			if (g) m->finish_grad(dL_dparams, gradient_mode, s);
-			HIP_CHECK(hipGetLastError());
-			return;
-		}
-		if (m->f32) {  // GridEncoding<float>::backward: kernel_grid_backward (float atomics) and dL_dinput from dy/dx
-			if (dL_dinput && !ctx->dydx.p) throw std::runtime_error("encoding backward: dL_dinput needs the forward's dy/dx");
-			if (g) HIP_CHECK(hipMemsetAsync(g, 0, (size_t)m->n_params() * 4, s));
-			launch_grid_f32_backward(s, n, t.gl, valid, input, (const float*)dL_doutput, m->layout, g, ctx->dydx.p, dL_dinput);
-			if (g) m->finish_grad(dL_dparams, gradient_mode, s);
-			HIP_CHECK(hipGetLastError());
-			return;
-		}
-		m->load_params(params, s);
-		if (m->kind == NeusModule::Network) {
-			// NerfNetwork::backward (nerf_network.h:330-601): first and second order in one pass; the Testbed's
-			// forward-recompute + backward writes every parameter gradient (Overwrite) into g
-			float* gg = g ? g : m->gtmp.p;
-			HIP_CHECK(hipMemsetAsync(gg, 0, (size_t)t.lay.P * 4, s));
-			const float saved = t.tbuf.indeed_batch;
-			t.tbuf.indeed_batch = (float)(m->indeed_batch ? m->indeed_batch : n);
-			t.tbuf.dpos = dL_dinput ? m->dpos.p : nullptr;
-			t.net_backward(nullptr, nullptr, n, input, valid, (const half_t*)dL_doutput, gg, s);
-			t.tbuf.dpos = nullptr;
-			t.tbuf.indeed_batch = saved;
-			if (dL_dinput) {  // position columns; dt and direction columns are 0 (the direction gradient is not propagated)
-				HIP_CHECK(hipMemset2DAsync(dL_dinput, COORD_W * 4, 0, COORD_W * 4, n, s));
-				HIP_CHECK(hipMemcpy2DAsync(dL_dinput, COORD_W * 4, m->dpos.p, 16, 12, n, hipMemcpyDeviceToDevice, s));
-			}
-		} else {
-			const half_t* dly = m->paired_in(dL_doutput, n, s);
-			if (dL_dinput) {
-				if (!ctx->dydx.p) throw std::runtime_error("encoding backward: dL_dinput needs the forward's dy/dx");
-				launch_enc_input_grad(s, n, n, t.lay.L, dly, ctx->dydx.p, dL_dinput, 3);
-			}
-			if (g)  // kernel_grid_backward (grid.h:371-500) through the fused binned scatter, second-order term zero
-				launch_grid_scatter(s, nullptr, n, n, input, 3, t.gl, valid, dly, m->zero_h.p, m->zero_v.p, g, t.swork,
-				                    t.scan_tmp.p, t.scan_tmp_bytes);
-		}
-		if (g) m->finish_grad(dL_dparams, gradient_mode, s);
+		m->finish_grad(g, n, dL_dparams, gradient_mode, s);
 		HIP_CHECK(hipGetLastError());
 	});
 }
 
+// NetworkWithInputEncoding::backward_backward_input (network_with_input_encoding.h:159-250): (1) the network's backward
+// gives dL/dX0 (parameter gradients ignored); (2) the encoding's backward_backward_input with it as dL_doutput: the
+// second-order encoding gradient, J_enc dL_ddLdinput into the network's front rows, and dL_dinput, the encoding's own
+// second-derivative term (the MLP's part is 0: act'' = 0); (3) the FullyFusedMLP's backward_backward_input on that front
+// (fully_fused_mlp.cu:1088-1198): its weight gradients and dL_ddLdoutput = J_mlp J_enc dL_ddLdinput. A stand-alone
+// encoding is step (2) alone on the caller's tensors.
 int neus_module_backward_backward_input(NeusModule* m, void* stream, const NeusContext* ctx, uint32_t n, const float* dL_ddLdinput,
                                         const float* input, const void* dL_doutput, void* dL_dparams, void* dL_ddLdoutput, float* dL_dinput,
                                         const void* params, int gradient_mode) {
 	return guard([&] {
-		if (m->kind == NeusModule::Network)
+		if (m->fused == NeusModule::Nerf)
 			throw std::runtime_error("NerfNetwork: the eikonal second-order term is part of backward (nerf_network.h:330-601); "
 			                         "backward_backward_input is provided by the HashGrid and network-with-input-encoding modules "
 			                         "(the reference's NerfNetwork does not implement it either: object.h:222-232)");
-		if (m->kind == NeusModule::Mlp) {
-			// NetworkWithInputEncoding::backward_backward_input (network_with_input_encoding.h:159-250) with the Identity
-			// encoding: its backward_backward_input (identity.h:182-206) turns dL_ddLdinput into the network's dL_ddLdinput
-			// (x scale; the padded rows, which the reference leaves uninitialised, are 0: the constant padding has no input
-			// gradient); FullyFusedMLP::backward_backward_input_impl (fully_fused_mlp.cu:1088-1198): fronts f_0 = u,
-			// f_i = act'(h_{i-1}) (W_{i-1} f_{i-1}); backs b_{N+2} = dL_doutput, b_i = act'(h_{i-2}) (W_{i-1}^T b_{i+1});
-			// dW_{i-1} = b_{i+1} f_{i-1}^T. dL_ddLdoutput = W_N f_N (the front carried through the output matrix); dL_dinput = 0:
-			// with act'' = 0 the first derivative is piecewise constant in the input.
-			if (!ctx || ctx->n != n || !ctx->acts.p) throw std::runtime_error("backward_backward_input: needs the forward's context");
-			if (!dL_ddLdinput || !dL_doutput || !params) throw std::runtime_error("backward_backward_input: null input");
-			m->check_n(n, true);
-			m->check_bbi_exact(dL_ddLdoutput, dL_dinput);
-			HIP_CHECK(hipSetDevice(m->core.device));
-			StreamSwap sw(m->core, stream);
-			hipStream_t s = m->core.stream;
-			float* g = m->grad_target(dL_dparams, gradient_mode);
-			if (dL_dinput) HIP_CHECK(hipMemsetAsync(dL_dinput, 0, (size_t)n * m->ff.n_in * 4, s));
-			if (!g && !dL_ddLdoutput) return;
-			const FfNet& f = m->ff;
-			launch_ff_input(s, n, f.n_in, f.in_pad, dL_ddLdinput, f.in_scale, 0.f, m->ff_front.p, true);
-			ff_bbi_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, g != nullptr, (half_t*)dL_ddLdoutput);
-			if (g) {
-				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
-				m->finish_grad(dL_dparams, gradient_mode, s);
-			}
-			HIP_CHECK(hipGetLastError());
-			return;
-		}
-		if (m->kind == NeusModule::PfEncoding) {
-			// dL_ddLdoutput = J u (first derivatives only); dL_dinput_d = u_d sum_k dL_doutput_k d2y_k/dx_d^2 (every feature
-			// depends on one input dim, except the spherical harmonics': refused)
-			if (!ctx || ctx->n != n) throw std::runtime_error("backward_backward_input: needs the forward's context");
-			if (!input || !dL_ddLdinput || (dL_dinput && !dL_doutput)) throw std::runtime_error("backward_backward_input: null input");
-			m->check_n(n, true);
-			m->check_bbi_sh(dL_dinput);
-			HIP_CHECK(hipSetDevice(m->core.device));
-			StreamSwap sw(m->core, stream);
-			hipStream_t s = m->core.stream;
-			if (dL_dinput) launch_pf_input_grad(s, m->pf, n, input, m->pf_view(dL_doutput, n), dL_ddLdinput, dL_dinput);
-			if (dL_ddLdoutput) launch_pf_out(s, m->pf, n, input, dL_ddLdinput, m->pf_view(dL_ddLdoutput, n));
-			HIP_CHECK(hipGetLastError());
-			return;
-		}
-		if (m->kind == NeusModule::EncMlp) {
-			// NetworkWithInputEncoding::backward_backward_input composed as GridMlp composes the HashGrid: the front J_enc u goes
-			// through the FullyFusedMLP's backward_backward_input (fully_fused_mlp.cu:1088-1198); dL_dinput is the encoding's own
-			// second-derivative term with the network's dL/dX0 as its dL_doutput (the MLP's part is 0: act'' = 0)
-			if (!ctx || ctx->n != n || !ctx->acts.p) throw std::runtime_error("backward_backward_input: needs the forward's context");
-			if (!input || !dL_ddLdinput || !dL_doutput || !params) throw std::runtime_error("backward_backward_input: null input");
-			m->check_n(n, true);
-			m->check_bbi_exact(dL_ddLdoutput, dL_dinput);
-			m->check_bbi_sh(dL_dinput);
-			HIP_CHECK(hipSetDevice(m->core.device));
-			StreamSwap sw(m->core, stream);
-			hipStream_t s = m->core.stream;
-			float* g = m->grad_target(dL_dparams, gradient_mode);
-			if (!g && !dL_ddLdoutput && !dL_dinput) return;
-			const FfNet& f = m->ff;
-			if (dL_dinput) {
-				const half_t* dX0 = ff_backward_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, nullptr, false);
-				launch_pf_input_grad(s, m->pf, n, input, PfView{const_cast<half_t*>(dX0), f.in_pad, 1, 0u}, dL_ddLdinput, dL_dinput);
-			}
-			if (g || dL_ddLdoutput) {
-				launch_pf_rows(s, m->pf, n, input, dL_ddLdinput, m->ff_front.p, f.in_pad);
-				ff_bbi_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, g != nullptr, (half_t*)dL_ddLdoutput);
-			}
-			if (g) {
-				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
-				m->finish_grad(dL_dparams, gradient_mode, s);
-			}
-			HIP_CHECK(hipGetLastError());
-			return;
-		}
-		if (m->kind == NeusModule::NdGrid) {
-			// GridEncoding::backward_backward_input (grid.h:880-1181) in one launch: the second-order dL_dparams (atomics into a zeroed
-			// buffer), dL_ddLdoutput = J u and dL_dinput (mixed terms, and the diagonal ones with Smoothstep)
-			if (!ctx || ctx->n != n) throw std::runtime_error("backward_backward_input: needs the forward's context");
-			if (!input || !dL_ddLdinput || !dL_doutput || !params) throw std::runtime_error("backward_backward_input: null input");
-			m->check_n(n, true);
-			HIP_CHECK(hipSetDevice(m->core.device));
-			StreamSwap sw(m->core, stream);
-			hipStream_t s = m->core.stream;
-			float* g = m->grad_target(dL_dparams, gradient_mode);
-			if (!g && !dL_ddLdoutput && !dL_dinput) return;
-			if (g) HIP_CHECK(hipMemsetAsync(g, 0, (size_t)m->n_params() * 4, s));
-			launch_grid_nd_bbi(s, n, m->nd, m->valid(), input, params, m->f32, dL_ddLdinput, m->nd_view(dL_doutput, n), g, m->nd_view(dL_ddLdoutput, n), 0,
-			                   dL_dinput ? m->nd_scratch() : nullptr, dL_dinput);
-			if (g) m->finish_grad(dL_dparams, gradient_mode, s);
-			HIP_CHECK(hipGetLastError());
-			return;
-		}
-		if (m->kind == NeusModule::NdGridMlp) {
-			// NetworkWithInputEncoding::backward_backward_input in the three steps of the GridMlp branch below: (1) the network's
-			// backward gives dL/dX0; (2) the grid's backward_backward_input with it as dL_doutput: the second-order grid gradient,
-			// J_enc u into the front rows, dL_dinput; (3) the FullyFusedMLP's backward_backward_input on that front
-			if (!ctx || ctx->n != n || !ctx->acts.p) throw std::runtime_error("backward_backward_input: needs the forward's context");
-			if (!input || !dL_ddLdinput || !dL_doutput || !params) throw std::runtime_error("backward_backward_input: null input");
-			m->check_n(n, true);
-			m->check_bbi_exact(dL_ddLdoutput, dL_dinput);
-			HIP_CHECK(hipSetDevice(m->core.device));
-			StreamSwap sw(m->core, stream);
-			hipStream_t s = m->core.stream;
-			float* g = m->grad_target(dL_dparams, gradient_mode);
-			if (!g && !dL_ddLdoutput && !dL_dinput) return;
-			const FfNet& f = m->ff;
-			const half_t* dX0 = nullptr;
-			if (g || dL_dinput) dX0 = ff_backward_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, nullptr, false);
-			const bool front = g || dL_ddLdoutput;
-			if (g) HIP_CHECK(hipMemsetAsync(g + f.P, 0, (size_t)(m->n_params() - f.P) * 4, s));
-			launch_grid_nd_bbi(s, n, m->nd, m->valid(), input, (const half_t*)params + f.P, false, dL_ddLdinput, m->nd_rows(dX0), g ? g + f.P : nullptr,
-			                   m->nd_rows(front ? m->ff_front.p : nullptr), f.in_pad - m->n_out_nd(), dL_dinput ? m->nd_scratch() : nullptr, dL_dinput);
-			if (front) ff_bbi_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, g != nullptr, (half_t*)dL_ddLdoutput);
-			if (g) {
-				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
-				m->finish_grad(dL_dparams, gradient_mode, s);
-			}
-			HIP_CHECK(hipGetLastError());
-			return;
-		}
-		if (m->kind == NeusModule::GridMlp) {
-			// NetworkWithInputEncoding::backward_backward_input (network_with_input_encoding.h:159-250): (1) the network's
-			// backward gives dL/d(encoding) (parameter gradients ignored); (2) the HashGrid's backward_backward_input with it as
-			// dL_doutput: the second-order grid gradient and pos_encoding_dy = dy/dx . dL_ddLdinput (grid.h:1697-1800); (3) the
-			// FullyFusedMLP's backward_backward_input with pos_encoding_dy as its dL_ddLdinput (fully_fused_mlp.cu:1088-1198).
-			// dL_ddLdoutput = the front through the output matrix (J_mlp J_enc dL_ddLdinput); dL_dinput = the HashGrid's second
-			// derivative in x (k_grid_ddx) with dL/d(encoding) as its dL_doutput.
-			if (!ctx || ctx->n != n || !ctx->dydx.p || !ctx->acts.p) throw std::runtime_error("backward_backward_input: needs the forward's context");
-			if (!input || !dL_ddLdinput || !dL_doutput || !params) throw std::runtime_error("backward_backward_input: null input");
-			m->check_n(n, true);
-			m->check_bbi_exact(dL_ddLdoutput, dL_dinput);
-			HIP_CHECK(hipSetDevice(m->core.device));
-			StreamSwap sw(m->core, stream);
-			NeusTestbed& t = m->core;
-			hipStream_t s = t.stream;
-			float* g = m->grad_target(dL_dparams, gradient_mode);
-			if (!g && !dL_ddLdoutput && !dL_dinput) return;
-			const FfNet& f = m->ff;
-			if (g || dL_dinput) {
-				const half_t* dX0 = ff_backward_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, nullptr, false);
-				launch_enc_from_rows(s, n, t.lay.L, dX0, f.in_pad, m->denc_tmp.p);
-			}
-			if (g || dL_ddLdoutput) launch_enc_ddLdoutput(s, n, n, t.lay.L, dL_ddLdinput, ctx->dydx.p, (half_t*)m->u_tmp.p, m->v4.p);
-			if (g)
-				launch_grid_scatter(s, nullptr, n, n, input, 3, t.gl, m->valid(), m->zero_h.p, (const half_t*)m->denc_tmp.p, m->v4.p, g + f.P,
-				                    t.swork, t.scan_tmp.p, t.scan_tmp_bytes);
-			if (dL_dinput)
-				launch_grid_ddx(s, n, n, input, t.gl, m->valid(), (const half_t*)params + f.P, (const half_t*)m->denc_tmp.p, dL_ddLdinput,
-				                m->ddx_scratch(), dL_dinput);
-			if (g || dL_ddLdoutput) {
-				launch_enc_to_rows(s, n, t.lay.L, m->u_tmp.p, m->ff_front.p, f.in_pad);
-				ff_bbi_chain(m, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, g != nullptr, (half_t*)dL_ddLdoutput);
-			}
-			if (g) {
-				launch_mlp_grad_reduce(s, MlpGradReduce{m->ff_partial.p, ff_wgrad_blocks(n), f.P, g, nullptr, nullptr, 0, m->ff_dummy.p});
-				m->finish_grad(dL_dparams, gradient_mode, s);
-			}
-			HIP_CHECK(hipGetLastError());
-			return;
-		}
-		if (m->kind == NeusModule::DensityNet) {
-			// NetworkWithInputEncoding::backward_backward_input (network_with_input_encoding.h:159-250): u = dy/dx . dL_ddLdinput
-			// (kernel_grid_backward_input_backward_dLdoutput), the MLP's backward-backward (fully_fused_mlp.cu:1088-1198: b2 =
-			// relu'(H0) W1^T dL, h1' = relu'(H0) W0 u; dW0 = b2 u^T, dW1 = dL h1'^T) and the encoding's second-order grid
-			// gradient with dL/d(encoding) = W0^T b2. dL_ddLdoutput = W1 h1' (one more MFMA of the fused kernel); dL_dinput = the
-			// HashGrid's second derivative in x (k_grid_ddx) with dL/d(encoding) as its dL_doutput.
-			if (!ctx || ctx->n != n || !ctx->dydx.p || !ctx->enc.p) throw std::runtime_error("backward_backward_input: needs the forward's context");
-			if (!input || !dL_ddLdinput || !dL_doutput || !params) throw std::runtime_error("backward_backward_input: null input");
-			m->check_n(n, true);
-			HIP_CHECK(hipSetDevice(m->core.device));
-			StreamSwap sw(m->core, stream);
-			NeusTestbed& t = m->core;
-			hipStream_t s = t.stream;
-			float* g = m->grad_target(dL_dparams, gradient_mode);
-			if (!g && !dL_ddLdoutput && !dL_dinput) return;
-			const half_t* ph = (const half_t*)params;
-			launch_enc_ddLdoutput(s, n, n, t.lay.L, dL_ddLdinput, ctx->dydx.p, (half_t*)m->u_tmp.p, m->v4.p);
-			DNetLaunch d{};
-			d.w0 = ph; d.w1 = ph + (size_t)m->dn_width * m->dn_de; d.enc = ctx->enc.p; d.dL = (const half_t*)dL_doutput; d.u = m->u_tmp.p;
-			d.denc = m->denc_tmp.p; d.wpartial = m->dn_partial.p; d.out = (half_t*)dL_ddLdoutput;
-			launch_dnet(s, t.lay.L, m->dn_width, 2, n, d);
-			if (g) {
-				launch_mlp_grad_reduce(s, MlpGradReduce{m->dn_partial.p, dnet_blocks(n), m->n_mlp, g, nullptr, nullptr, 0, m->dn_dummy.p});
-				launch_grid_scatter(s, nullptr, n, n, input, 3, t.gl, m->valid(), m->zero_h.p, (const half_t*)m->denc_tmp.p, m->v4.p, g + m->n_mlp,
-				                    t.swork, t.scan_tmp.p, t.scan_tmp_bytes);
-			}
-			if (dL_dinput)
-				launch_grid_ddx(s, n, n, input, t.gl, m->valid(), ph + m->n_mlp, (const half_t*)m->denc_tmp.p, dL_ddLdinput, m->ddx_scratch(),
-				                dL_dinput);
-			if (g) m->finish_grad(dL_dparams, gradient_mode, s);
-			HIP_CHECK(hipGetLastError());
-			return;
-		}
-		if (!ctx || ctx->n != n || !ctx->dydx.p) throw std::runtime_error("backward_backward_input: needs the forward's context (dy/dx)");
-		if (!input || !dL_ddLdinput || !dL_doutput) throw std::runtime_error("backward_backward_input: null input");
+		if (!ctx || ctx->n != n || !m->ctx_ok(ctx))
+			throw std::runtime_error(std::string("backward_backward_input: needs the forward's context") + (!m->ff.P && m->enc.keeps_dydx() ? " (dy/dx)" : ""));
+		if (!dL_ddLdinput || !m->enc.bbi_args(input, dL_doutput, params, dL_dinput) || (m->ff.P && (!dL_doutput || !params)))
+			throw std::runtime_error("backward_backward_input: null input");
 		m->check_n(n, true);
+		m->check_bbi_exact(dL_ddLdoutput, dL_dinput);
+		m->enc.check_bbi_sh(dL_dinput);
 		HIP_CHECK(hipSetDevice(m->core.device));
 		StreamSwap sw(m->core, stream);
-		NeusTestbed& t = m->core;
-		hipStream_t s = t.stream;
+		hipStream_t s = m->core.stream;
 		float* g = m->grad_target(dL_dparams, gradient_mode);
-		if (m->f32) {  // GridEncoding<float>::backward_backward_input (grid.h:880-1007 with GRAD_T = float)
-			if (g) HIP_CHECK(hipMemsetAsync(g, 0, (size_t)m->n_params() * 4, s));
-			launch_grid_f32_bbi(s, n, t.gl, m->valid(), input, dL_ddLdinput, (const float*)dL_doutput, m->layout, g, ctx->dydx.p, (float*)dL_ddLdoutput);
-			if (dL_dinput) {  // kernel_grid_backward_input_backward_input (grid.h:1010-1181)
-				if (!params) throw std::runtime_error("module: null params");
-				launch_grid_f32_ddx(s, n, t.gl, m->valid(), input, (const float*)params, (const float*)dL_doutput, m->layout, dL_ddLdinput,
-				                    m->ddx_scratch(), dL_dinput);
+		if (!g && !dL_ddLdoutput && !dL_dinput) return;
+		if (m->fused == NeusModule::Dnet) dnet_bbi(m, s, n, ctx, input, dL_ddLdinput, dL_doutput, params, g, dL_ddLdoutput, dL_dinput);
+		else {
+			const FfNet& f = m->ff;
+			const bool net = m->net();
+			float* ge = g && m->enc.n_params() ? g + m->enc_off : nullptr;
+			EncIO dy = enc_io(dL_doutput, 0), Ju = enc_io(dL_ddLdoutput, 0);
+			if (net) {
+				dy = enc_io(nullptr, f.in_pad);
+				if (m->enc.bbi_reads_dy(ge, dL_dinput))
+					dy.p = const_cast<half_t*>(ff_backward_chain(f, m->fw, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, nullptr, false,
+					                                             FfSink{false, nullptr, 1.f}));
+				Ju = enc_io(g || dL_ddLdoutput ? m->fw.front.p : nullptr, f.in_pad);
 			}
-			if (g) m->finish_grad(dL_dparams, gradient_mode, s);
-			HIP_CHECK(hipGetLastError());
-			return;
+			m->enc.backward_backward(s, n, ctx, input, dL_ddLdinput, dy, m->enc_params(params), ge, Ju, dL_dinput);
+			if (net && Ju.p) ff_bbi_chain(f, m->fw, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, g != nullptr, (half_t*)dL_ddLdoutput);
 		}
-		// dL_ddLdoutput (kernel_grid_backward_input_backward_dLdoutput) and dL_ddLdinput as float4 for the scatter
-		const bool relay = m->layout != ENC_LAYOUT_PAIRED && dL_ddLdoutput;
-		launch_enc_ddLdoutput(s, n, n, t.lay.L, dL_ddLdinput, ctx->dydx.p, relay ? (half_t*)m->enc_tmp.p : (half_t*)dL_ddLdoutput, m->v4.p);
-		if (relay) launch_enc_to_layout(s, n, t.lay.L, m->enc_tmp.p, (half_t*)dL_ddLdoutput, m->layout);
-		if (g || dL_dinput) {
-			m->load_params(params, s);
-			const half_t* dly = m->paired_in(dL_doutput, n, s);
-			// kernel_grid_backward_input_backward_grid (grid.h:880-1007): the fused scatter's second-order term with
-			// g = dL_doutput, v = dL_ddLdinput, first-order term zero
-			if (g)
-				launch_grid_scatter(s, nullptr, n, n, input, 3, t.gl, m->valid(), m->zero_h.p, dly, m->v4.p, g, t.swork,
-				                    t.scan_tmp.p, t.scan_tmp_bytes);
-			if (dL_dinput)  // kernel_grid_backward_input_backward_input (grid.h:1010-1181)
-				launch_grid_ddx(s, n, n, input, t.gl, m->valid(), t.params_h.p + t.lay.grid_off, dly, dL_ddLdinput, m->ddx_scratch(), dL_dinput);
-			if (g) m->finish_grad(dL_dparams, gradient_mode, s);
-		}
+		m->finish_grad(g, n, dL_dparams, gradient_mode, s);
 		HIP_CHECK(hipGetLastError());
 	});
 }
