@@ -509,9 +509,16 @@ int neus_debug_host_group_allreduce(NeusHostGroup* group, void* host, uint64_t n
  * non-null, dL_dparams = dS/dparams (by gradient_mode), dL_ddLdoutput = dS/d(dL_doutput) (the output's shape and precision; the
  * encoding's in its output layout) and dL_dinput = dS/dinput ([n][n_input_dims] f32, overwritten; a sample's levels are summed in
  * level order without atomics, so two calls agree bitwise; all zeros for create_network, whose first derivative is piecewise
- * constant). The network chains carry no second derivative of an activation: dL_ddLdoutput and dL_dinput are exact, and
- * accepted, only for hidden activation ReLU or None with output activation None (ReLU'' = 0); for any other network a non-null
- * dL_ddLdoutput or dL_dinput is an error and the parameter gradients (both pointers null) stay available.
+ * constant). By default ("second_order": "tcnn") the network chains carry no second derivative of an activation, as
+ * tcnn's: dL_ddLdoutput and dL_dinput are exact, and accepted, only for hidden activation ReLU or None with output activation
+ * None (ReLU'' = 0); for any other network a non-null dL_ddLdoutput or dL_dinput is an error and the parameter gradients
+ * (both pointers null) stay available, without their act'' terms (behind a grid, an output activation other than None is
+ * an error there too: that chain has no forward output for its backward). A network config with "second_order": "exact" (this
+ * build's key, echoed by hyperparams only when set) adds those terms for Softplus, Squareplus, Sigmoid and Exponential,
+ * hidden or on the output: all three results are then the exact derivatives of S for every network, the backs start from
+ * the output activation's delta, dL_dinput also carries the network's own curvature pushed back through the encoding's
+ * first-order backward (behind the Identity encoding it is no longer zero), and only a SphericalHarmonics segment's
+ * dL_dinput stays refused. For ReLU / None with a linear output "exact" runs the default's launches, bit for bit.
  * Progressive levels follow set_training_step (grid.h:2427-2437; 0 = all levels). */
 typedef struct NeusModule NeusModule;
 typedef struct NeusContext NeusContext;

@@ -45,13 +45,41 @@ __device__ __forceinline__ float ff_dact(uint32_t act, float y) {
 	default: return 1.f;
 	}
 }
+// the second derivative act''(x), also from the post-activation value y (0 for ReLU and None)
+__device__ __forceinline__ float ff_d2act(uint32_t act, float y) {
+	switch (act) {
+	case FF_EXP: return y;
+	case FF_SIGMOID: return y * (1.0f - y) * (1.0f - 2.0f * y);
+	case FF_SQUAREPLUS: { const float t = y * FF_K_ACT, q = t * t + 1; return 2.0f * FF_K_ACT * t * t * t / (q * q * q); }
+	case FF_SOFTPLUS: { const float p = 1.0f - expf(-y * FF_K_ACT); return FF_K_ACT * p * (1.0f - p); }
+	default: return 0.f;
+	}
+}
+// four consecutive fp16 of a row as floats / back (accumulator registers 4j .. 4j + 3 are four consecutive output rows)
+__device__ __forceinline__ void ff_load4(const half_t* p, float v[4]) {
+	const h4 x = *(const h4*)p;
+#pragma unroll
+	for (int k = 0; k < 4; ++k) v[k] = (float)x[k];
+}
+__device__ __forceinline__ void ff_store4(half_t* p, const float v[4]) {
+	h4 x;
+#pragma unroll
+	for (int k = 0; k < 4; ++k) x[k] = (half_t)v[k];
+	*(h4*)p = x;
+}
 }  // namespace
 
 // Out[s][o] = f(sum_k A[o][k] In[s][k]), o < O, k < K (multiple of 16), A = W [O][K] or (trans) W^T with W [K][O].
 //   mode FF_MODE_ACT : f = act on the fp16-rounded sum, fp16 out
 //   mode FF_MODE_DACT: f = (fp16 sum) * dact(aux[s][o]) rounded to fp16, fp16 out
 //   mode FF_MODE_F32 : float out = (float)(fp16 sum), written for o < o_lim only
-__global__ void __launch_bounds__(256) k_ff_layer(FfLayer L) {
+// With d = dact(aux[s][o]) and c = d2act(aux[s][o]), the exact double backward's epilogues (fp16 out, O a multiple of 4):
+//   mode FF_MODE_DACT with out2: out2 = the fp16 sum itself, beside out (the front pass keeps p, the back pass t)
+//   mode FF_MODE_CURV    : out = c p[s][o] t[s][o] + d (fp16 sum): the curvature adjoint of a hidden layer in one pass
+//   mode FF_MODE_OUT_CURV: out = d (fp16 sum) (skipped when null), out2 = c (fp16 sum) t[s][o]: the output layer's
+//                          dL_ddLdoutput and curvature adjoint from the front carried through the last matrix
+// One instantiation per mode: the MFMA body is shared, and no epilogue holds another's registers.
+template <uint32_t MODE> __global__ void __launch_bounds__(256) k_ff_layer(FfLayer L) {
 	extern __shared__ half_t s_w[];
 	const uint32_t Op = (L.O + 31) / 32 * 32, lda = L.K + 8;
 	// stage A [Op][K] (+ 8 halves of row padding); rows >= O are zero
@@ -64,7 +92,7 @@ __global__ void __launch_bounds__(256) k_ff_layer(FfLayer L) {
 	__syncthreads();
 	const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
 	const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-	const uint32_t MT = Op / 32, KS = L.K / 16;
+	const uint32_t MT = Op / 32, KS = L.in ? L.K / 16 : 0;
 	for (uint32_t s0 = wave * 32; s0 < L.n; s0 += n_waves * 32) {
 		const uint32_t s = s0 + r;
 		const bool valid = s < L.n;
@@ -84,28 +112,56 @@ __global__ void __launch_bounds__(256) k_ff_layer(FfLayer L) {
 			}
 		}
 		if (!valid) continue;
+		if constexpr (MODE != FF_MODE_ACT && MODE != FF_MODE_F32) {
+			// O is a multiple of 4 here (launch_ff_layer): registers 4j .. 4j + 3 are rows o0 .. o0 + 3, so every operand of the
+			// epilogue is one 8-byte load and every result one 8-byte store per lane
 #pragma unroll
-		for (int mt = 0; mt < 4; ++mt) {
-			if ((uint32_t)mt >= MT) break;
+			for (int mt = 0; mt < 4; ++mt) {
+				if ((uint32_t)mt >= MT) break;
 #pragma unroll
-			for (int i = 0; i < 16; ++i) {
-				const uint32_t o = 32 * mt + ff_row(i, h);
-				if (o >= L.O) continue;
-				const float x = (float)(half_t)acc[mt][i];
-				if (L.mode == FF_MODE_F32) {
-					if (o < L.o_lim) L.out_f[(size_t)s * L.ldo + o] = x * L.out_scale;
-				} else if (L.mode == FF_MODE_DACT) {
-					const float d = (float)(half_t)ff_dact(L.act, (float)L.aux[(size_t)s * L.ldx + o]);
-					L.out[(size_t)s * L.ldo + o] = (half_t)(x * d);
-				} else {
-					L.out[(size_t)s * L.ldo + o] = (half_t)ff_act(L.act, x);
+				for (int j = 0; j < 4; ++j) {
+					const uint32_t o0 = 32 * mt + ff_row(4 * j, h);
+					if (o0 >= L.O) continue;
+					const size_t at = (size_t)s * L.ldo + o0;
+					float x[4], y[4], r0[4], r1[4], pv[4], tv[4];
+					ff_load4(L.aux + (size_t)s * L.ldx + o0, y);
+					if constexpr (MODE == FF_MODE_CURV) ff_load4(L.p + at, pv);
+					if constexpr (MODE != FF_MODE_DACT) ff_load4(L.t + at, tv);
+#pragma unroll
+					for (int k = 0; k < 4; ++k) {
+						x[k] = (float)(half_t)acc[mt][4 * j + k];
+						const float d = (float)(half_t)ff_dact(L.act, y[k]);
+						r0[k] = x[k] * d;
+						if constexpr (MODE == FF_MODE_CURV) r0[k] = ff_d2act(L.act, y[k]) * pv[k] * tv[k] + r0[k];
+						if constexpr (MODE == FF_MODE_OUT_CURV) r1[k] = ff_d2act(L.act, y[k]) * x[k] * tv[k];
+						else r1[k] = x[k];
+					}
+					if (L.out) ff_store4(L.out + at, r0);
+					if (L.out2) ff_store4(L.out2 + at, r1);
+				}
+			}
+		} else {
+#pragma unroll
+			for (int mt = 0; mt < 4; ++mt) {
+				if ((uint32_t)mt >= MT) break;
+#pragma unroll
+				for (int i = 0; i < 16; ++i) {
+					const uint32_t o = 32 * mt + ff_row(i, h);
+					if (o >= L.O) continue;
+					const float x = (float)(half_t)acc[mt][i];
+					if constexpr (MODE == FF_MODE_F32) {
+						if (o < L.o_lim) L.out_f[(size_t)s * L.ldo + o] = x * L.out_scale;
+					} else {
+						L.out[(size_t)s * L.ldo + o] = (half_t)ff_act(L.act, x);
+					}
 				}
 			}
 		}
 	}
 }
 
-// dW[o][i] (partial over this block's samples) = sum_s D[s][o] X[s][i] -> prow[block][off + o I + i] (fp32)
+// dW[o][i] (partial over this block's samples) = sum_s D[s][o] X[s][i] (+ D2[s][o] X2[s][i], chunk by chunk after the first
+// product: the exact double backward's curvature term) -> prow[block][off + o I + i] (fp32)
 __global__ void __launch_bounds__(256) k_ff_wgrad(FfWgrad G) {
 	extern __shared__ half_t s_t[];
 	const uint32_t Op = (G.O + 31) / 32 * 32, Ip = (G.I + 31) / 32 * 32;
@@ -120,15 +176,19 @@ __global__ void __launch_bounds__(256) k_ff_wgrad(FfWgrad G) {
 	for (int t = 0; t < 4; ++t)
 #pragma unroll
 		for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
-	for (uint32_t c0 = b0; c0 < b1; c0 += 32) {
+	const uint32_t n_prod = G.D2 ? 2 : 1;  // the chunk's second product follows its first into the same accumulators
+	for (uint32_t c0 = b0; c0 < b1; c0 += 32)
+	for (uint32_t pr = 0; pr < n_prod; ++pr) {
+		const half_t* D = pr ? G.D2 : G.D;
+		const half_t* X = pr ? G.X2 : G.X;
 		__syncthreads();
 		for (uint32_t e = threadIdx.x; e < 32 * Op; e += blockDim.x) {
 			const uint32_t k = e / Op, o = e % Op, s = c0 + k;
-			Dt[o * 40 + k] = (s < b1 && o < G.O) ? G.D[(size_t)s * G.ldd + o] : (half_t)0.f;
+			Dt[o * 40 + k] = (s < b1 && o < G.O) ? D[(size_t)s * G.ldd + o] : (half_t)0.f;
 		}
 		for (uint32_t e = threadIdx.x; e < 32 * Ip; e += blockDim.x) {
 			const uint32_t k = e / Ip, i = e % Ip, s = c0 + k;
-			Xt[i * 40 + k] = (s < b1 && i < G.I) ? G.X[(size_t)s * G.ldx + i] : (half_t)0.f;
+			Xt[i * 40 + k] = (s < b1 && i < G.I) ? X[(size_t)s * G.ldx + i] : (half_t)0.f;
 		}
 		__syncthreads();
 #pragma unroll
@@ -182,12 +242,28 @@ static uint32_t ff_blocks(uint64_t n, uint32_t per, uint32_t cap) { return (uint
 
 void launch_ff_layer(hipStream_t s, const FfLayer& L) {
 	if (L.K % 16 || L.K == 0 || L.O == 0 || L.O > 128) throw std::runtime_error("ff layer: K must be a multiple of 16, 1 <= O <= 128");
+	if (L.mode > FF_MODE_OUT_CURV || (!L.in && L.mode != FF_MODE_CURV)) throw std::runtime_error("ff layer: unknown mode / null input");
+	if (L.mode != FF_MODE_ACT && L.mode != FF_MODE_F32) {  // the vector epilogue: whole groups of four rows, 8-byte aligned rows
+		const auto al8 = [](const void* p) { return ((uintptr_t)p & 7) == 0; };
+		if (L.O % 4 || L.ldo % 4 || L.ldx % 4 || !L.aux || !al8(L.aux) || !al8(L.out) || !al8(L.out2) || !al8(L.p) || !al8(L.t))
+			throw std::runtime_error("ff layer: the derivative epilogues need O and the row strides multiples of 4 and 8-byte aligned tensors");
+		if ((L.mode == FF_MODE_DACT && !L.out) || (L.mode == FF_MODE_CURV && (!L.out || !L.p || !L.t)) || (L.mode == FF_MODE_OUT_CURV && (!L.out2 || !L.t)))
+			throw std::runtime_error("ff layer: a tensor of the epilogue is null");
+	}
 	const size_t smem = (size_t)((L.O + 31) / 32 * 32) * (L.K + 8) * sizeof(half_t);
-	k_ff_layer<<<ff_blocks(L.n, 128, 1024), 256, smem, s>>>(L);
+	const uint32_t blocks = ff_blocks(L.n, 128, 1024);
+	switch (L.mode) {
+	case FF_MODE_ACT: k_ff_layer<FF_MODE_ACT><<<blocks, 256, smem, s>>>(L); break;
+	case FF_MODE_DACT: k_ff_layer<FF_MODE_DACT><<<blocks, 256, smem, s>>>(L); break;
+	case FF_MODE_F32: k_ff_layer<FF_MODE_F32><<<blocks, 256, smem, s>>>(L); break;
+	case FF_MODE_CURV: k_ff_layer<FF_MODE_CURV><<<blocks, 256, smem, s>>>(L); break;
+	default: k_ff_layer<FF_MODE_OUT_CURV><<<blocks, 256, smem, s>>>(L); break;
+	}
 }
 uint32_t ff_wgrad_blocks(uint32_t n) { return ff_blocks(n, 1024, 512); }
 void launch_ff_wgrad(hipStream_t s, const FfWgrad& G) {
 	if (G.O == 0 || G.I == 0 || G.O > 128 || G.I > 128) throw std::runtime_error("ff wgrad: 1..128 rows and columns");
+	if (!G.D2 != !G.X2) throw std::runtime_error("ff wgrad: the second product needs both of its factors");
 	const size_t smem = (size_t)((G.O + 31) / 32 * 32 + (G.I + 31) / 32 * 32) * 40 * sizeof(half_t);
 	k_ff_wgrad<<<ff_wgrad_blocks(G.n), 256, smem, s>>>(G);
 }

@@ -267,20 +267,24 @@ uint32_t dnet_blocks(uint32_t n);  // the grid of launch_dnet (= the partial row
 void launch_dnet(hipStream_t s, uint32_t L, uint32_t W, int mode /* 0 fwd, 1 bwd, 2 bwd-bwd */, uint32_t n, const DNetLaunch& d);
 // ffmlp.hip: tcnn FullyFusedMLP behind the Identity encoding (cpp_api.cu:170-172, the network of create_network)
 enum : uint32_t { FF_NONE = 0, FF_RELU = 1, FF_EXP = 2, FF_SIGMOID = 3, FF_SQUAREPLUS = 4, FF_SOFTPLUS = 5 };
-enum : uint32_t { FF_MODE_ACT = 0, FF_MODE_DACT = 1, FF_MODE_F32 = 2 };
+// k_ff_layer's epilogues. The last two carry the curvature (act'') terms of the exact double backward.
+enum : uint32_t { FF_MODE_ACT = 0, FF_MODE_DACT = 1, FF_MODE_F32 = 2, FF_MODE_CURV = 3, FF_MODE_OUT_CURV = 4 };
 struct FfLayer {
 	const half_t* W; uint32_t O, K; uint32_t trans;  // A = W [O][K] or (trans) W^T of W [K][O]
-	const half_t* in; uint32_t ldi;                    // [n][ldi] fp16
-	half_t* out; float* out_f; uint32_t ldo, o_lim;    // [n][ldo] fp16 (modes ACT, DACT) or f32 (mode F32, o < o_lim)
+	const half_t* in; uint32_t ldi;                    // [n][ldi] fp16 (mode CURV: null = no product, the sum is 0)
+	half_t* out; float* out_f; uint32_t ldo, o_lim;    // [n][ldo] fp16 or f32 (mode F32, o < o_lim); mode OUT_CURV: out may be null
 	float out_scale = 1.f;                             // mode F32: the fp16-rounded sum times this (an Identity encoding's scale)
-	const half_t* aux; uint32_t ldx;                   // mode DACT: forward post-activation values [n][ldx]
+	const half_t* aux; uint32_t ldx;                   // modes DACT, CURV, OUT_CURV: forward post-activation values [n][ldx]
 	uint32_t mode, act, n;
+	half_t* out2;                                      // [n][ldo]: mode DACT: the fp16 sum itself (null: not kept); mode OUT_CURV: see ffmlp.hip
+	const half_t* p; const half_t* t;                  // [n][ldo]: mode CURV: both factors of the act'' term; mode OUT_CURV: t
 };
 struct FfWgrad {
 	const half_t* D; uint32_t ldd, O;                  // [n][ldd] deltas
 	const half_t* X; uint32_t ldx, I;                  // [n][ldx] layer inputs
 	float* partial; uint32_t ld_partial, off;          // partial rows [blocks][ld_partial], this matrix at off (O x I)
 	uint32_t n;
+	const half_t* D2; const half_t* X2;                // a second product D2^T X2 (same shapes and strides) into the same sums; null: none
 };
 void launch_ff_layer(hipStream_t s, const FfLayer& L);
 uint32_t ff_wgrad_blocks(uint32_t n);  // blocks (= partial rows) of launch_ff_wgrad for n samples

@@ -3254,6 +3254,10 @@ struct FfNet {
 	uint32_t W = 0, N = 0, n_in = 0, in_pad = 0, n_out = 0, out_pad = 0, act = FF_RELU, out_act = FF_NONE;
 	std::vector<uint32_t> off, rows, cols;
 	uint32_t P = 0;
+	bool exact = false;  // "second_order": "exact": backward_backward_input carries the act'' terms
+	// where act'' != 0: the hidden activation / any of the two (only then does an exact module differ from a default one)
+	bool hidden_curved() const { return act != FF_RELU && act != FF_NONE; }
+	bool curved() const { return exact && (hidden_curved() || out_act != FF_NONE); }
 	void build() {
 		off.clear(); rows.clear(); cols.clear(); P = 0;
 		for (uint32_t l = 0; l <= N; ++l) {
@@ -3292,18 +3296,25 @@ FfNet ff_from_json(const JsonValue& j, uint32_t n_input_dims, uint32_t n_output_
 	f.n_out = n_output_dims; f.out_pad = (n_output_dims + 15) / 16 * 16;
 	f.act = FfNet::activation(j.string("activation", "ReLU"));
 	f.out_act = FfNet::activation(j.string("output_activation", "None"));
+	const std::string so = j.string("second_order", "tcnn");
+	if (so != "tcnn" && so != "exact") throw std::runtime_error("FullyFusedMLP: second_order must be tcnn or exact, but got '" + so + "'");
+	f.exact = so == "exact";
 	f.build();
 	return f;
 }
 std::string ff_hyper(const FfNet& f) {
 	static const char* an[6] = {"None", "ReLU", "Exponential", "Sigmoid", "Squareplus", "Softplus"};
 	return "{\"otype\": \"FullyFusedMLP\", \"n_neurons\": " + std::to_string(f.W) + ", \"n_hidden_layers\": " + std::to_string(f.N) +
-	       ", \"activation\": \"" + an[f.act] + "\", \"output_activation\": \"" + an[f.out_act] + "\"}";
+	       ", \"activation\": \"" + an[f.act] + "\", \"output_activation\": \"" + an[f.out_act] + "\"" +
+	       (f.exact ? ", \"second_order\": \"exact\"" : "") + "}";
 }
 // the network's workspace for one batch of `capacity` samples: inference activations, backward-backward fronts, the delta
-// ping-pong and the per-block weight-gradient rows
+// ping-pong and the per-block weight-gradient rows; for a network with act'' terms (FfNet::curved) also the curvature
+// adjoints' ping-pong e, the fronts before their activation derivative p [N][n][W] and one layer's back before its t [n][W]
+// (hidden act'' != 0), and the output y [n][out_pad], recomputed for the output activation's derivatives
 struct FfWork {
 	Dev<half_t> acts, front, d[2];
+	Dev<half_t> e[2], p, t, y;
 	Dev<float> partial, dummy;
 	void alloc(const FfNet& f, uint32_t capacity) {
 		acts.alloc(f.acts_halves(capacity));
@@ -3312,6 +3323,10 @@ struct FfWork {
 		d[0].alloc((size_t)capacity * dmax); d[1].alloc((size_t)capacity * dmax);
 		partial.alloc((size_t)ff_wgrad_blocks(capacity) * f.P);
 		dummy.alloc(4);
+		if (!f.curved()) return;
+		e[0].alloc((size_t)capacity * dmax); e[1].alloc((size_t)capacity * dmax);
+		if (f.hidden_curved()) { p.alloc((size_t)capacity * f.N * f.W); t.alloc((size_t)capacity * f.W); }
+		if (f.out_act != FF_NONE) y.alloc((size_t)capacity * f.out_pad);
 	}
 };
 // where the backward's layer 0 puts dL/d(network input): fp16 rows [n][in_pad] for the encoding's backward, or, behind the
@@ -3341,17 +3356,24 @@ void ff_forward(const FfNet& f, hipStream_t s, uint32_t n, const void* params, h
 		x = L.out; ldx = f.W;
 	}
 }
-// delta through layer l (l >= 1) to the input of layer l: act'(h_{l-1}) (W_l^T d)
+// the output y = out_act(W_N h_N) again from a forward's activations (bitwise the forward's): the values its derivatives are taken from
+void ff_output(const FfNet& f, hipStream_t s, uint32_t n, const void* params, const half_t* acts, half_t* y) {
+	FfLayer L = ff_layer(ff_mat(f, params, f.N), f.rows[f.N], f.cols[f.N], false, ff_hidden(f, acts, n, f.N - 1), f.W, n);
+	L.mode = FF_MODE_ACT; L.act = f.out_act; L.out = y; L.ldo = f.out_pad;
+	launch_ff_layer(s, L);
+}
+// delta through layer l (l >= 1) to the input of layer l: act'(h_{l-1}) (W_l^T d); keep (when given): W_l^T d itself
 void ff_back_through(const FfNet& f, hipStream_t s, uint32_t n, const void* params, uint32_t l, const half_t* d, uint32_t ldd, const half_t* acts_fwd,
-                     half_t* out) {
+                     half_t* out, half_t* keep = nullptr) {
 	FfLayer L = ff_layer(ff_mat(f, params, l), f.cols[l], f.rows[l], true, d, ldd, n);
-	L.mode = FF_MODE_DACT; L.act = f.act; L.out = out; L.ldo = f.W;
+	L.mode = FF_MODE_DACT; L.act = f.act; L.out = out; L.out2 = keep; L.ldo = f.W;
 	L.aux = ff_hidden(f, acts_fwd, n, l - 1); L.ldx = f.W;
 	launch_ff_layer(s, L);
 }
-void ff_wgrad(const FfNet& f, hipStream_t s, uint32_t n, uint32_t l, const half_t* d, uint32_t ldd, const half_t* x, uint32_t ldx, float* partial) {
+void ff_wgrad(const FfNet& f, hipStream_t s, uint32_t n, uint32_t l, const half_t* d, uint32_t ldd, const half_t* x, uint32_t ldx, float* partial,
+              const half_t* d2 = nullptr, const half_t* x2 = nullptr) {
 	FfWgrad G{};
-	G.D = d; G.ldd = ldd; G.O = f.rows[l]; G.X = x; G.ldx = ldx; G.I = f.cols[l];
+	G.D = d; G.ldd = ldd; G.O = f.rows[l]; G.X = x; G.ldx = ldx; G.I = f.cols[l]; G.D2 = d2; G.X2 = x2;
 	G.partial = partial; G.ld_partial = f.P; G.off = f.off[l]; G.n = n;
 	launch_ff_wgrad(s, G);
 }
@@ -3387,33 +3409,71 @@ const half_t* ff_backward_chain(const FfNet& f, FfWork& w, hipStream_t s, uint32
 // FullyFusedMLP::backward_backward_input_impl (fully_fused_mlp.cu:1088-1198) with the front f_0 = the network's
 // dL_ddLdinput already in w.front as rows [n][in_pad]: fronts f_i = act'(h_{i-1}) (W_{i-1} f_{i-1}); dL_ddLdoutput (when
 // asked for) = the front carried through the output matrix, f_{N+1} = W_N f_N, as [n][out_pad] fp16; with wgrad the backs
-// b_{N+2} = dL_doutput, b_i = act'(h_{i-2}) (W_{i-1}^T b_{i+1}) and dW_{i-1} = b_{i+1} f_{i-1}^T into the partials
-void ff_bbi_chain(const FfNet& f, FfWork& w, hipStream_t s, uint32_t n, const void* params, const half_t* acts, const half_t* dL_doutput, bool wgrad,
-                  half_t* dL_ddLdoutput) {
+// b_{N+2} = dL_doutput, b_i = act'(h_{i-2}) (W_{i-1}^T b_{i+1}) and dW_{i-1} = b_{i+1} f_{i-1}^T into the partials.
+//
+// That chain is exact where act'' = 0. For a network with act'' terms (FfNet::curved; the output y is in w.y) it becomes the
+// exact one. With z the pre-activations, p_i = W_{i-1} f_{i-1} the fronts before their derivative (kept beside f_i), the backs
+// started from the output delta d_o = dL_doutput act_o'(z_o) and t_i = W_i^T d_{i+1} the backs before theirs (kept beside d_i):
+//   dL_ddLdoutput = act_o'(z_o) p_o,   e_o = act_o''(z_o) p_o dL_doutput                   (one epilogue of the last front)
+//   e_i = act''(z_i) p_i t_i + act'(z_i) (W_i^T e_{i+1})                                   (one epilogue per hidden layer)
+//   dW_{i-1} = d_i f_{i-1}^T + e_i h_{i-1}^T                                               (both products in one launch)
+// and q = W_0^T e_1 = d(dL_ddLdinput . dL/dx)/dX0 along the forward path leaves through the sink when want_q: behind the
+// Identity encoding x scale into dL_dinput, else as fp16 rows [n][in_pad] (returned) for the encoding's backward.
+const half_t* ff_bbi_chain(const FfNet& f, FfWork& w, hipStream_t s, uint32_t n, const void* params, const half_t* acts, const half_t* dL_doutput,
+                           bool wgrad, half_t* dL_ddLdoutput, bool want_q = false, const FfSink& sink = FfSink{false, nullptr, 1.f}) {
+	const bool cv = f.curved(), hc = cv && f.hidden_curved(), oc = cv && f.out_act != FF_NONE;
 	half_t* fr = w.front.p;
 	auto front = [&](uint32_t i) { return i == 0 ? fr : fr + (size_t)n * f.in_pad + (size_t)(i - 1) * n * f.W; };
+	auto kept_p = [&](uint32_t i) { return w.p.p + (size_t)(i - 1) * n * f.W; };
 	for (uint32_t i = 1; i <= f.N; ++i) {
 		FfLayer L = ff_layer(ff_mat(f, params, i - 1), f.rows[i - 1], f.cols[i - 1], false, front(i - 1), i == 1 ? f.in_pad : f.W, n);
 		L.mode = FF_MODE_DACT; L.act = f.act; L.out = front(i); L.ldo = f.W;
 		L.aux = ff_hidden(f, acts, n, i - 1); L.ldx = f.W;
+		if (hc) L.out2 = kept_p(i);
 		launch_ff_layer(s, L);
 	}
-	if (dL_ddLdoutput) {
+	want_q = want_q && cv;
+	const half_t* e = nullptr;  // the curvature adjoint entering the layer below
+	int ep = 0;
+	if (oc && (dL_ddLdoutput || wgrad || want_q)) {
+		FfLayer L = ff_layer(ff_mat(f, params, f.N), f.rows[f.N], f.cols[f.N], false, front(f.N), f.W, n);
+		L.mode = FF_MODE_OUT_CURV; L.act = f.out_act; L.out = dL_ddLdoutput; L.out2 = w.e[0].p; L.ldo = f.out_pad;
+		L.aux = w.y.p; L.ldx = f.out_pad; L.t = dL_doutput;
+		launch_ff_layer(s, L);
+		e = w.e[0].p; ep = 1;
+	} else if (dL_ddLdoutput) {
 		FfLayer L = ff_layer(ff_mat(f, params, f.N), f.rows[f.N], f.cols[f.N], false, front(f.N), f.W, n);
 		L.mode = FF_MODE_ACT; L.act = FF_NONE; L.out = dL_ddLdoutput; L.ldo = f.out_pad;
 		launch_ff_layer(s, L);
 	}
-	if (!wgrad) return;
+	if (!wgrad && !want_q) return nullptr;
 	const half_t* b = dL_doutput;
 	uint32_t ldb = f.out_pad;
 	int pp = 0;
+	if (oc) { launch_ff_out_delta(s, n, f.out_pad, f.out_act, b, w.y.p, w.d[0].p); b = w.d[0].p; pp = 1; }
 	for (uint32_t l = f.N + 1; l-- > 0;) {
-		ff_wgrad(f, s, n, l, b, ldb, front(l), l == 0 ? f.in_pad : f.W, w.partial.p);
+		if (wgrad) ff_wgrad(f, s, n, l, b, ldb, front(l), l == 0 ? f.in_pad : f.W, w.partial.p, e, e ? (l == 0 ? acts : ff_hidden(f, acts, n, l - 1)) : nullptr);
 		if (l > 0) {
-			ff_back_through(f, s, n, params, l, b, ldb, acts, w.d[pp].p);
+			if (wgrad || hc) ff_back_through(f, s, n, params, l, b, ldb, acts, w.d[pp].p, hc ? w.t.p : nullptr);  // d_l, and t_l for the act'' term
+			if (hc) {  // e_l; below a linear output there is no e_{l+1}: no product
+				FfLayer L = ff_layer(ff_mat(f, params, l), f.cols[l], f.rows[l], true, e, ldb, n);
+				L.mode = FF_MODE_CURV; L.act = f.act; L.out = w.e[ep].p; L.ldo = f.W;
+				L.aux = ff_hidden(f, acts, n, l - 1); L.ldx = f.W; L.p = kept_p(l); L.t = w.t.p;
+				launch_ff_layer(s, L);
+			} else if (e) {
+				ff_back_through(f, s, n, params, l, e, ldb, acts, w.e[ep].p);
+			}
+			if (hc || e) { e = w.e[ep].p; ep ^= 1; }
 			b = w.d[pp].p; pp ^= 1; ldb = f.W;
+		} else if (want_q && (!sink.direct || sink.dL_dinput)) {
+			FfLayer L = ff_layer(ff_mat(f, params, 0), f.in_pad, f.W, true, e, ldb, n);
+			if (sink.direct) { L.mode = FF_MODE_F32; L.out_f = sink.dL_dinput; L.ldo = f.n_in; L.o_lim = f.n_in; L.out_scale = sink.scale; }
+			else { L.mode = FF_MODE_ACT; L.act = FF_NONE; L.out = w.e[ep].p; L.ldo = f.in_pad; }
+			launch_ff_layer(s, L);
+			return sink.direct ? nullptr : w.e[ep].p;
 		}
 	}
+	return nullptr;
 }
 // the weight gradients from the per-block partials (fixed order), into the head of g
 void ff_reduce(const FfNet& f, FfWork& w, hipStream_t s, uint32_t n_blocks, float* g) {
@@ -3547,6 +3607,7 @@ struct Enc : EncSpec {
 	Dev<float4> v4, zero_v;           // Hash16: dL_ddLdinput as float4 / the scatter's absent second-order term
 	Dev<half_t> zero_h;
 	Dev<float> partial;               // the grids: dL_dinput's per-level terms [n_in L][capacity] (first use)
+	Dev<float> dx_tmp;                // in front of a network with act'' terms: the forward-path part of dL_dinput [capacity][n_in] (first use)
 
 	// ---- description
 	bool keeps_dydx() const { return type == Hash16 || type == Hash32; }
@@ -3753,15 +3814,16 @@ struct Enc : EncSpec {
 	}
 	// GridEncoding::backward_backward_input (grid.h:880-1181) and its parameter-free counterparts. u = dL_ddLdinput, dy =
 	// dL/d(encoding output): the second-order parameter gradient into g, J u into Ju (the caller's dL_ddLdoutput or the
-	// network's front rows) and dL_dinput; each is skipped when null
+	// network's front rows) and dL_dinput; each is skipped when null. `curved`: a network with act'' terms follows, whose
+	// chain's q = dS/dX0 comes back through backward_curved: what that call completes is left to it
 	void backward_backward(hipStream_t s, uint32_t n, const NeusContext* ctx, const float* input, const float* u, EncIO dy, const void* params, float* g,
-	                       EncIO Ju, float* dL_dinput) {
+	                       EncIO Ju, float* dL_dinput, bool curved = false) {
 		switch (type) {
 		case Identity:
 			// identity.h:182-206: the network's dL_ddLdinput = scale x u (the padded rows, which the reference leaves uninitialised,
 			// are 0: the constant padding has no input gradient); dL_dinput = 0: with act'' = 0 the first derivative is piecewise
-			// constant in the input
-			if (dL_dinput) HIP_CHECK(hipMemsetAsync(dL_dinput, 0, (size_t)n * n_in * 4, s));
+			// constant in the input (curved: the network's chain writes scale x q)
+			if (dL_dinput && !curved) HIP_CHECK(hipMemsetAsync(dL_dinput, 0, (size_t)n * n_in * 4, s));
 			if (Ju.p) launch_ff_input(s, n, n_in, Ju.ld, u, scale, 0.f, (half_t*)Ju.p, true);
 			break;
 		case Pf:
@@ -3778,7 +3840,7 @@ struct Enc : EncSpec {
 				const half_t* dly = (const half_t*)denc_tmp.p;
 				if (dy.p) launch_enc_from_rows(s, n, L(), (const half_t*)dy.p, dy.ld, denc_tmp.p);
 				if (g || Ju.p) launch_enc_ddLdoutput(s, n, n, L(), u, ctx->dydx.p, (half_t*)u_tmp.p, v4.p);
-				if (g) hash_scatter(s, n, input, zero_h.p, dly, v4.p, g);
+				if (g && !curved) hash_scatter(s, n, input, zero_h.p, dly, v4.p, g);  // curved: with q as its first-order cotangent
 				if (dL_dinput) hash_ddx(s, n, input, (const half_t*)params, dly, u, dL_dinput);
 				if (Ju.p) launch_enc_to_rows(s, n, L(), u_tmp.p, (half_t*)Ju.p, Ju.ld);
 			} else {
@@ -3805,6 +3867,30 @@ struct Enc : EncSpec {
 			                   dL_dinput);
 			break;
 		}
+	}
+	// The rest of backward_backward in front of a network with act'' terms: q = dS/dX0 [n][q.ld] from the network's chain
+	// goes through this encoding's first-order backward, J_theta^T q added into g and J^T q into dL_dinput
+	void backward_curved(hipStream_t s, uint32_t n, const NeusContext* ctx, const float* input, EncIO q, const void* params, float* g, float* dL_dinput) {
+		float* dx = nullptr;
+		if (dL_dinput && type != Identity) { dx_tmp.alloc((size_t)n_in * capacity); dx = dx_tmp.p; }
+		switch (type) {
+		case Pf:
+			if (dx) launch_pf_input_grad(s, pf, n, input, view(q, n), nullptr, dx);
+			break;
+		case Hash16: {  // the deferred scatter takes q beside the second-order cotangent (denc_tmp, v4: backward_backward's)
+			if (!g && !dx) break;
+			launch_enc_from_rows(s, n, L(), (const half_t*)q.p, q.ld, enc_tmp.p);
+			if (g) hash_scatter(s, n, input, (const half_t*)enc_tmp.p, (const half_t*)denc_tmp.p, v4.p, g);
+			if (dx) launch_enc_input_grad(s, n, n, L(), (const half_t*)enc_tmp.p, ctx->dydx.p, dx, 3);
+			break;
+		}
+		case Nd:  // atomics on top of backward_backward's: its memset stands for both
+			if (g) launch_grid_nd_backward(s, n, nd, valid(), input, view(q, n), g);
+			if (dx) launch_grid_nd_input_grad(s, n, nd, valid(), input, params, false, view(q, n), scratch(), dx);
+			break;
+		default: break;  // Identity: the network's layer 0 wrote dL_dinput (FfSink)
+		}
+		if (dx) launch_add_f32(s, n * n_in, dx, dL_dinput);
 	}
 };
 
@@ -3888,7 +3974,7 @@ struct NeusModule {
 	// backward_backward_input's dL_ddLdoutput / dL_dinput of a network: the fronts / backs chain has no act'' term, so they
 	// are exact only where act'' = 0 (hidden ReLU or None) and the output is linear
 	void check_bbi_exact(const void* dL_ddLdoutput, const float* dL_dinput) const {
-		if (!ff.P || (!dL_ddLdoutput && !dL_dinput)) return;
+		if (!ff.P || ff.exact || (!dL_ddLdoutput && !dL_dinput)) return;
 		if ((ff.act == FF_RELU || ff.act == FF_NONE) && ff.out_act == FF_NONE) return;
 		throw std::runtime_error("backward_backward_input: dL_ddLdoutput and dL_dinput are exact only for hidden activation ReLU or None with "
 		                         "output activation None (the second derivative of any other activation is not implemented); pass null "
@@ -3912,7 +3998,8 @@ static bool precision_f32(int requested_precision) {
 	return requested_precision == NEUS_PRECISION_FP32;
 }
 // A module of the parsed parts with its options (this build's keys, beside tcnn's): "gradient_precision": "fp16" (default,
-// tcnn's param precision) | "fp32"; encoding "output_layout": "AoS" (default: cpp::Module's column-major view) | "SoA" | "paired"
+// tcnn's param precision) | "fp32"; encoding "output_layout": "AoS" (default: cpp::Module's column-major view) | "SoA" | "paired";
+// network "second_order": "tcnn" (default: tcnn's double-backward chain, without act'') | "exact" (ff_from_json)
 static std::unique_ptr<NeusModule> new_module(const EncSpec& e, const FfNet& f, const JsonValue& j, uint32_t batch_capacity) {
 	int dev = 0;
 	HIP_CHECK(hipGetDevice(&dev));
@@ -4273,6 +4360,11 @@ int neus_module_backward(NeusModule* m, void* stream, const NeusContext* ctx, ui
 // second-derivative term (the MLP's part is 0: act'' = 0); (3) the FullyFusedMLP's backward_backward_input on that front
 // (fully_fused_mlp.cu:1088-1198): its weight gradients and dL_ddLdoutput = J_mlp J_enc dL_ddLdinput. A stand-alone
 // encoding is step (2) alone on the caller's tensors.
+// A network created with "second_order": "exact" whose hidden or output activation has a second derivative (FfNet::curved)
+// runs the exact chain instead (ff_bbi_chain): step (1) starts from the output activation's delta, step (3) also runs when
+// only dL_dinput is asked for and returns q = dS/dX0 along the forward path, and (4) the encoding's first-order backward of
+// q is added to its parameter gradient and to dL_dinput (Enc::backward_curved; behind the Identity encoding layer 0 writes
+// scale x q itself). The fp16 HashGrid's scatter waits for q and takes both cotangents in its one call.
 int neus_module_backward_backward_input(NeusModule* m, void* stream, const NeusContext* ctx, uint32_t n, const float* dL_ddLdinput,
                                         const float* input, const void* dL_doutput, void* dL_dparams, void* dL_ddLdoutput, float* dL_dinput,
                                         const void* params, int gradient_mode) {
@@ -4299,15 +4391,25 @@ int neus_module_backward_backward_input(NeusModule* m, void* stream, const NeusC
 			const bool net = m->net();
 			float* ge = g && m->enc.n_params() ? g + m->enc_off : nullptr;
 			EncIO dy = enc_io(dL_doutput, 0), Ju = enc_io(dL_ddLdoutput, 0);
+			const bool curved = net && f.curved();  // act'' terms: dL_dinput needs the fronts too, and the chain's q the encoding's backward
 			if (net) {
 				dy = enc_io(nullptr, f.in_pad);
+				// the default chain has no forward output to take the output activation's delta from (the call does not receive it)
+				if (!curved && f.out_act != FF_NONE && m->enc.bbi_reads_dy(ge, dL_dinput))
+					throw std::runtime_error("backward_backward_input: an output activation other than None behind this encoding needs the network's "
+					                         "\"second_order\": \"exact\" (the default chain has no forward output for its backward)");
+				if (curved && f.out_act != FF_NONE) ff_output(f, s, n, params, ctx->acts.p, m->fw.y.p);
 				if (m->enc.bbi_reads_dy(ge, dL_dinput))
-					dy.p = const_cast<half_t*>(ff_backward_chain(f, m->fw, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, nullptr, false,
-					                                             FfSink{false, nullptr, 1.f}));
-				Ju = enc_io(g || dL_ddLdoutput ? m->fw.front.p : nullptr, f.in_pad);
+					dy.p = const_cast<half_t*>(ff_backward_chain(f, m->fw, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, curved ? m->fw.y.p : nullptr,
+					                                             false, FfSink{false, nullptr, 1.f}));
+				Ju = enc_io(g || dL_ddLdoutput || (curved && dL_dinput) ? m->fw.front.p : nullptr, f.in_pad);
 			}
-			m->enc.backward_backward(s, n, ctx, input, dL_ddLdinput, dy, m->enc_params(params), ge, Ju, dL_dinput);
-			if (net && Ju.p) ff_bbi_chain(f, m->fw, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, g != nullptr, (half_t*)dL_ddLdoutput);
+			m->enc.backward_backward(s, n, ctx, input, dL_ddLdinput, dy, m->enc_params(params), ge, Ju, dL_dinput, curved);
+			if (net && Ju.p) {
+				const half_t* q = ff_bbi_chain(f, m->fw, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, g != nullptr, (half_t*)dL_ddLdoutput,
+				                               ge || dL_dinput, m->enc.sink(dL_dinput));
+				if (q) m->enc.backward_curved(s, n, ctx, input, enc_io(q, f.in_pad), m->enc_params(params), ge, dL_dinput);
+			}
 		}
 		m->finish_grad(g, n, dL_dparams, gradient_mode, s);
 		HIP_CHECK(hipGetLastError());

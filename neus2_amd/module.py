@@ -209,9 +209,11 @@ class Module:
     def backward_backward_input(self, ctx, x, dL_ddLdinput, dL_doutput, params, dL_dparams=None, dL_ddLdoutput=None,
                                 mode=GradientMode.Overwrite, dL_dinput=None):
         """With S = dL_ddLdinput . dL/dx: dL_dparams = dS/dparams, dL_ddLdoutput = dS/d(dL_doutput) (the output's shape and
-        precision) and dL_dinput = dS/dx ([n, n_input_dims] f32), each written only when given. The last two are provided
-        for hidden activation ReLU / None with a linear output (an error otherwise); dL_dinput is not provided with a
-        SphericalHarmonics segment in the encoding (an error: no second derivative of it is implemented)."""
+        precision) and dL_dinput = dS/dx ([n, n_input_dims] f32), each written only when given. By default the last two are
+        provided for hidden activation ReLU / None with a linear output (an error otherwise); a network created with
+        "second_order": "exact" in its config carries the act'' terms and gives all three exactly for every activation.
+        dL_dinput is not provided with a SphericalHarmonics segment in the encoding (an error: no second derivative of it
+        is implemented)."""
         if self.kind == "network":
             raise NeusError("backward_backward_input: the NerfNetwork's second order is inside backward")
         check(lib().neus_module_backward_backward_input(self._h, _stream(), ctx._h, C.c_uint32(ctx.n), _p(dL_ddLdinput), _p(x),

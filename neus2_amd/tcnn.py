@@ -7,9 +7,11 @@ Each class is a torch.nn.Module with one fp32 `params` Parameter. forward(x) tak
 pads B with zero rows to a multiple of 128 (the kernels' batch granularity) and returns [B, n_output_dims]. Autograd is
 complete to second order in the input: `grad(y, x, create_graph=True)` followed by `.backward()` (an eikonal loss) gives
 gradients for `params`, `x` and the first gradient's `grad_outputs`, through neus_module_backward_backward_input. The
-double backward is provided for hidden activation ReLU / None with a linear output (ReLU'' = 0) and for encodings without
-a SphericalHarmonics segment (no second derivative of it is implemented); a cotangent for the parameter gradient (a
-gradient of a gradient in the parameters) is not supported.
+double backward is exact for every hidden and output activation of the FullyFusedMLP (the networks are created with
+"second_order": "exact", which adds the act'' terms of Softplus, Squareplus, Sigmoid and Exponential to tiny-cuda-nn's
+chain; for ReLU / None with a linear output the two coincide) and is provided for encodings without a SphericalHarmonics
+segment (no second derivative of it is implemented); a cotangent for the parameter gradient (a gradient of a gradient in
+the parameters) is not supported.
 
 Encodings: grids (HashGrid / Grid / DenseGrid / TiledGrid: 2, 3 or 4 input dims, 1, 2, 4 or 8 features per level, "type" Hash /
 Dense / Tiled, "interpolation" Linear / Smoothstep; with Smoothstep the double backward carries the grid's diagonal second
@@ -56,10 +58,9 @@ class NativeBackend:
         fp32 = self.m.precision == "fp32"
         self.param_dtype = self.output_dtype = torch.float32 if fp32 else torch.float16
         hp = self.m.hyperparams()
-        net, enc = hp.get("network"), hp.get("encoding", hp)
+        enc = hp.get("encoding", hp)
         has_sh = any(e.get("otype") == "SphericalHarmonics" for e in [enc] + list(enc.get("nested", [])))
-        self.supports_double_backward = not has_sh and (
-            net is None or (net["activation"] in ("ReLU", "None") and net["output_activation"] == "None"))
+        self.supports_double_backward = not has_sh
 
     def with_capacity(self, n):
         if n <= self.batch_capacity:
@@ -140,9 +141,8 @@ class _Backward(torch.autograd.Function):
             return (None,) * 9
         be = ctx.be
         if not be.supports_double_backward:
-            raise RuntimeError("double backward is not supported for this network: it is provided for hidden activation ReLU or None "
-                               "with output activation None (no second derivative of another activation is implemented) and for "
-                               "encodings without a SphericalHarmonics segment")
+            raise RuntimeError("double backward is not supported for this module: it is provided for encodings without a "
+                               "SphericalHarmonics segment (no second derivative of the spherical harmonics is implemented)")
         x, p, g = ctx.saved_tensors
         dp, ddy, dx = be.bwd_bwd_input(ctx.nctx, x, p, u.detach().float().contiguous(), g, want_p, want_g, want_x)
         inv = 1.0 / ctx.loss_scale
@@ -236,7 +236,7 @@ class Network(Module):
     """Network(n_input_dims, n_output_dims, network_config, seed=1337): a FullyFusedMLP on the raw input."""
 
     def __init__(self, n_input_dims, n_output_dims, network_config, seed=1337):
-        self.network_config = dict(_text(network_config), gradient_precision="fp32")
+        self.network_config = dict(_text(network_config), gradient_precision="fp32", second_order="exact")
         self._n_in, self._n_out = int(n_input_dims), int(n_output_dims)
         super().__init__(seed=seed, n_output_dims=self._n_out)
 
@@ -254,7 +254,7 @@ class NetworkWithInputEncoding(Module):
 
     def __init__(self, n_input_dims, n_output_dims, encoding_config, network_config, seed=1337):
         self.encoding_config = _text(encoding_config)
-        self.network_config = dict(_text(network_config), gradient_precision="fp32")
+        self.network_config = dict(_text(network_config), gradient_precision="fp32", second_order="exact")
         self._n_in, self._n_out = int(n_input_dims), int(n_output_dims)
         super().__init__(seed=seed, n_output_dims=self._n_out)
 
