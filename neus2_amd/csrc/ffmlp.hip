@@ -11,6 +11,10 @@
 // layer and dL/dinput. Weight gradients dW = D^T X sum over samples with the sample on the MFMA k axis: both operands are
 // staged transposed through LDS, per-block fp32 partial rows, summed in a fixed block order by k_mlp_grad_reduce
 // (deterministic, where tcnn's split-K fp16 GEMM is not).
+//
+// A CutlassMLP (my_tcnn src/cutlass_mlp.cu) is the same network at any width up to 512. Matrices of at most 128 x 128 take
+// the two kernels above; larger ones take k_ff_layer_wide / k_ff_wgrad_wide below, which tile the output rows over the
+// grid and stage the reduction axis in chunks, with the same arithmetic per element.
 #include "kernels.h"
 #include <algorithm>
 #include <stdexcept>
@@ -218,7 +222,251 @@ __global__ void __launch_bounds__(256) k_ff_wgrad(FfWgrad G) {
 	}
 }
 
-// Identity encoding (identity.h:44-70): X0[s][k] = (half)(in[s][k] scale + offset) for k < n_in, 1 for the padding
+// ---------------------------------------------------------------- wide matrices (CutlassMLP widths above 128)
+// The same products for O or K (wgrad: O or I) above 128, where neither the whole matrix nor a whole partial row fits a
+// block. Output rows are tiled over the grid and the reduction axis is staged through LDS in chunks of 64.
+namespace {
+constexpr uint32_t FF_WIDE_LAYER_BLOCKS = 512;  // sample blocks of k_ff_layer_wide's grid (x): beyond 2^17 samples a block takes a second trip
+constexpr uint32_t FF_WIDE_SLICES = 32;         // sample slices (= partial rows) of k_ff_wgrad_wide at most
+constexpr uint32_t FFW_OT = 128;           // output rows (wgrad: rows and columns) of a block
+constexpr uint32_t FFW_KC = 64;            // reduction elements staged at a time
+constexpr uint32_t FFW_RS = FFW_KC + 8;    // row stride of a [row][k] image: 16-byte reads, as k_ff_layer's s_w
+// row stride of a [k][row] image: 320 B = 16 dwords mod 64, so the four k rows x 64 B that a half-wave reads through one
+// transposing read land on distinct banks
+constexpr uint32_t FFW_TS = FFW_OT + 32;
+constexpr uint32_t FFW_IMG = FFW_KC * FFW_TS;  // halves of one image (>= FFW_OT * FFW_RS)
+static_assert(FFW_IMG >= FFW_OT * FFW_RS, "one LDS image serves both layouts");
+typedef __fp16 ff_trh4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
+
+// The MFMA operand of lane (r, h): img[k0 + 8 h .. + 7][c0 + r] of a [k][row] image, through ds_read_b64_tr_b16. Each
+// group of 16 lanes reads 4 k rows x 16 columns and gets them column-major: lane 4 q + p of the group points at k row q,
+// columns 4 p .. 4 p + 3, and lane i receives column i with k row q in element q. Groups 0 / 1 are columns 0-15 / 16-31
+// of h = 0, groups 2 / 3 those of h = 1. Every lane of the wave must be active.
+__device__ __forceinline__ h8 ff_frag_tr(const half_t* img, uint32_t k0, uint32_t c0, int lane) {
+	const int li = lane & 15, g = lane >> 4;
+	const half_t* p = img + (k0 + 8 * (g >> 1) + (li >> 2)) * FFW_TS + c0 + 16 * (g & 1) + 4 * (li & 3);
+	typedef __attribute__((address_space(3))) ff_trh4* lds_ptr;
+	const h4 lo = __builtin_bit_cast(h4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_ptr)p));
+	const h4 hi = __builtin_bit_cast(h4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_ptr)(p + 4 * FFW_TS)));
+	return (h8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+// Staging goes through registers, 4 x 16 bytes per thread of a 256-thread block, so that the next chunk's global loads are
+// in flight while the MFMAs read the current one from LDS.
+// rows [r0, r0 + FFW_KC) x columns [c0, c0 + FFW_OT) of the row-major src [.][ld], to become a [k][row] image; rows >= r1
+// and columns >= c1 (a multiple of 8) are zero
+__device__ __forceinline__ void ff_get_rows(h8 (&v)[4], const half_t* __restrict__ src, uint32_t ld, uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1) {
+#pragma unroll
+	for (int q = 0; q < 4; ++q) {
+		const uint32_t e = threadIdx.x + 256 * q, k = e / (FFW_OT / 8), c = c0 + 8 * (e % (FFW_OT / 8));
+		v[q] = (h8){0, 0, 0, 0, 0, 0, 0, 0};
+		if (r0 + k < r1 && c < c1) v[q] = *(const h8*)(src + (size_t)(r0 + k) * ld + c);
+	}
+}
+__device__ __forceinline__ void ff_put_rows(half_t* img, const h8 (&v)[4]) {
+#pragma unroll
+	for (int q = 0; q < 4; ++q) {
+		const uint32_t e = threadIdx.x + 256 * q;
+		*(h8*)(img + e / (FFW_OT / 8) * FFW_TS + 8 * (e % (FFW_OT / 8))) = v[q];
+	}
+}
+// rows [r0, r0 + FFW_OT) x columns [c0, c0 + FFW_KC) of the row-major src [.][ld], to become a [row][k] image; rows >= r1
+// and columns >= c1 (a multiple of 8) are zero
+__device__ __forceinline__ void ff_get_cols(h8 (&v)[4], const half_t* __restrict__ src, uint32_t ld, uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1) {
+#pragma unroll
+	for (int q = 0; q < 4; ++q) {
+		const uint32_t e = threadIdx.x + 256 * q, o = e / (FFW_KC / 8), c = c0 + 8 * (e % (FFW_KC / 8));
+		v[q] = (h8){0, 0, 0, 0, 0, 0, 0, 0};
+		if (r0 + o < r1 && c < c1) v[q] = *(const h8*)(src + (size_t)(r0 + o) * ld + c);
+	}
+}
+__device__ __forceinline__ void ff_put_cols(half_t* img, const h8 (&v)[4]) {
+#pragma unroll
+	for (int q = 0; q < 4; ++q) {
+		const uint32_t e = threadIdx.x + 256 * q;
+		*(h8*)(img + e / (FFW_KC / 8) * FFW_RS + 8 * (e % (FFW_KC / 8))) = v[q];
+	}
+}
+}  // namespace
+
+// k_ff_layer's epilogues on one sample's 4 row tiles from row o_blk on (the same arithmetic, statement for statement)
+template <uint32_t MODE>
+__device__ __forceinline__ void ff_wide_epilogue(const FfLayer& L, const f16v (&acc)[4], uint32_t s, uint32_t o_blk, uint32_t MT, int h) {
+	if constexpr (MODE != FF_MODE_ACT && MODE != FF_MODE_F32) {
+		// as k_ff_layer: O is a multiple of 4, registers 4j .. 4j + 3 are four consecutive rows
+#pragma unroll
+		for (int mt = 0; mt < 4; ++mt) {
+			if ((uint32_t)mt >= MT) break;
+#pragma unroll
+			for (int j = 0; j < 4; ++j) {
+				const uint32_t o0 = o_blk + 32 * mt + ff_row(4 * j, h);
+				if (o0 >= L.O) continue;
+				const size_t at = (size_t)s * L.ldo + o0;
+				float x[4], y[4], r0[4], r1[4], pv[4], tv[4];
+				ff_load4(L.aux + (size_t)s * L.ldx + o0, y);
+				if constexpr (MODE == FF_MODE_CURV) ff_load4(L.p + at, pv);
+				if constexpr (MODE != FF_MODE_DACT) ff_load4(L.t + at, tv);
+#pragma unroll
+				for (int k = 0; k < 4; ++k) {
+					x[k] = (float)(half_t)acc[mt][4 * j + k];
+					const float d = (float)(half_t)ff_dact(L.act, y[k]);
+					r0[k] = x[k] * d;
+					if constexpr (MODE == FF_MODE_CURV) r0[k] = ff_d2act(L.act, y[k]) * pv[k] * tv[k] + r0[k];
+					if constexpr (MODE == FF_MODE_OUT_CURV) r1[k] = ff_d2act(L.act, y[k]) * x[k] * tv[k];
+					else r1[k] = x[k];
+				}
+				if (L.out) ff_store4(L.out + at, r0);
+				if (L.out2) ff_store4(L.out2 + at, r1);
+			}
+		}
+	} else {
+#pragma unroll
+		for (int mt = 0; mt < 4; ++mt) {
+			if ((uint32_t)mt >= MT) break;
+#pragma unroll
+			for (int i = 0; i < 16; ++i) {
+				const uint32_t o = o_blk + 32 * mt + ff_row(i, h);
+				if (o >= L.O) continue;
+				const float x = (float)(half_t)acc[mt][i];
+				if constexpr (MODE == FF_MODE_F32) {
+					if (o < L.o_lim) L.out_f[(size_t)s * L.ldo + o] = x * L.out_scale;
+				} else {
+					L.out[(size_t)s * L.ldo + o] = (half_t)ff_act(L.act, x);
+				}
+			}
+		}
+	}
+}
+
+// k_ff_layer's product and epilogues (the same arithmetic: fp32 accumulation over all of K, one rounding to fp16, the
+// epilogue on that value) for one 128-row tile of the output (blockIdx.y) and 256 samples at a time: each wave holds
+// 64 samples x 4 row tiles. The matrix tile comes through LDS 64 k at a time: W [O][K] as a [row][k] image read 16 bytes
+// per lane; W^T of W [K][O] (TRANS) as the [k][row] image of its rows as they lie in memory, read transposed. A wave's
+// input fragments of a chunk are loaded before the chunk is staged, and the matrix tile of the next chunk into registers
+// while the MFMAs run on the current one.
+template <uint32_t MODE, bool TRANS> __global__ void __launch_bounds__(256) k_ff_layer_wide(FfLayer L) {
+	__shared__ __attribute__((aligned(16))) half_t s_a[FFW_IMG];
+	const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5, wv = threadIdx.x >> 6;
+	const uint32_t o_blk = blockIdx.y * FFW_OT;
+	const uint32_t MT = min(4u, (L.O - o_blk + 31) / 32), K = L.in ? L.K : 0;
+	for (uint32_t g0 = blockIdx.x * 256; g0 < L.n; g0 += gridDim.x * 256) {
+		const uint32_t sb = g0 + 64 * wv;
+		f16v acc[2][4];
+#pragma unroll
+		for (int g = 0; g < 2; ++g)
+#pragma unroll
+			for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+				for (int i = 0; i < 16; ++i) acc[g][mt][i] = 0.f;
+		// this thread's part of the matrix tile of chunk k0
+		const auto load_tile = [&](uint32_t k0, h8 (&va)[4]) {
+			const uint32_t k1 = min(K, k0 + FFW_KC);
+			if constexpr (TRANS) ff_get_rows(va, L.W, L.O, k0, k1, o_blk, L.O);
+			else ff_get_cols(va, L.W, L.K, o_blk, L.O, k0, k1);
+		};
+		h8 va[4];
+		if (K) load_tile(0, va);
+		for (uint32_t k0 = 0; k0 < K; k0 += FFW_KC) {
+			const uint32_t kc = min(FFW_KC, K - k0);
+			h8 b[2][4];  // this wave's input fragments: zero past the chunk's end and for rows >= n
+#pragma unroll
+			for (int g = 0; g < 2; ++g)
+#pragma unroll
+				for (int ks = 0; ks < 4; ++ks) {
+					const uint32_t s = sb + 32 * g + r;
+					b[g][ks] = (h8){0, 0, 0, 0, 0, 0, 0, 0};
+					if (s < L.n && 16u * ks < kc) b[g][ks] = *(const h8*)(L.in + (size_t)s * L.ldi + k0 + 16 * ks + 8 * h);
+				}
+			__syncthreads();  // the chunk before has been read
+			if constexpr (TRANS) ff_put_rows(s_a, va);
+			else ff_put_cols(s_a, va);
+			__syncthreads();
+			if (k0 + FFW_KC < K) load_tile(k0 + FFW_KC, va);  // in flight over this chunk's MFMAs
+#pragma unroll
+			for (int ks = 0; ks < 4; ++ks) {
+				if (16u * ks >= kc) break;
+#pragma unroll
+				for (int mt = 0; mt < 4; ++mt) {
+					if ((uint32_t)mt >= MT) break;
+					h8 a;
+					if constexpr (TRANS) a = ff_frag_tr(s_a, 16 * ks, 32 * mt, lane);
+					else a = *(const h8*)(s_a + (32 * mt + r) * FFW_RS + 16 * ks + 8 * h);
+					acc[0][mt] = ff_mfma(a, b[0][ks], acc[0][mt]);
+					acc[1][mt] = ff_mfma(a, b[1][ks], acc[1][mt]);
+				}
+			}
+		}
+		if (sb + r < L.n) ff_wide_epilogue<MODE>(L, acc[0], sb + r, o_blk, MT, h);
+		if (sb + 32 + r < L.n) ff_wide_epilogue<MODE>(L, acc[1], sb + 32 + r, o_blk, MT, h);
+	}
+}
+
+// k_ff_wgrad's sums for one 128 x 128 tile of dW (blockIdx.x) over one slice of `per` samples (blockIdx.y) ->
+// prow[slice][off + o I + i]. The deltas and the layer inputs of 64 samples are staged as they lie in memory ([sample][row]
+// images, the sample being the MFMA k axis) and both operands are read transposed; the next 64 samples are loaded into
+// registers meanwhile. Each wave owns 64 x 64 of the tile and skips the 32 x 32 parts that lie outside the matrix.
+__global__ void __launch_bounds__(256) k_ff_wgrad_wide(FfWgrad G, uint32_t per) {
+	__shared__ __attribute__((aligned(16))) half_t s_d[FFW_IMG], s_x[FFW_IMG];
+	const uint32_t TI = (G.I + FFW_OT - 1) / FFW_OT;
+	const uint32_t o_blk = blockIdx.x / TI * FFW_OT, i_blk = blockIdx.x % TI * FFW_OT;
+	const uint32_t b0 = blockIdx.y * per, b1 = min(G.n, b0 + per);
+	const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5, wv = threadIdx.x >> 6;
+	const uint32_t wo = 64 * (wv >> 1), wi = 64 * (wv & 1);
+	bool on[2][2];
+#pragma unroll
+	for (int a = 0; a < 2; ++a)
+#pragma unroll
+		for (int b = 0; b < 2; ++b) on[a][b] = o_blk + wo + 32 * a < G.O && i_blk + wi + 32 * b < G.I;
+	f16v acc[2][2];
+#pragma unroll
+	for (int a = 0; a < 2; ++a)
+#pragma unroll
+		for (int b = 0; b < 2; ++b)
+#pragma unroll
+			for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+	const uint32_t n_prod = G.D2 ? 2 : 1;  // the chunk's second product follows its first into the same accumulators
+	const uint32_t n_it = b0 < b1 ? (b1 - b0 + FFW_KC - 1) / FFW_KC * n_prod : 0;
+	const auto load_chunk = [&](uint32_t it, h8 (&vd)[4], h8 (&vx)[4]) {
+		const uint32_t c0 = b0 + it / n_prod * FFW_KC, pr = it % n_prod;
+		ff_get_rows(vd, pr ? G.D2 : G.D, G.ldd, c0, b1, o_blk, G.O);
+		ff_get_rows(vx, pr ? G.X2 : G.X, G.ldx, c0, b1, i_blk, G.I);
+	};
+	h8 vd[4], vx[4];
+	if (n_it) load_chunk(0, vd, vx);
+	for (uint32_t it = 0; it < n_it; ++it) {
+		const uint32_t c0 = b0 + it / n_prod * FFW_KC;
+		__syncthreads();
+		ff_put_rows(s_d, vd);
+		ff_put_rows(s_x, vx);
+		__syncthreads();
+		if (it + 1 < n_it) load_chunk(it + 1, vd, vx);  // in flight over this chunk's MFMAs
+#pragma unroll
+		for (int ks = 0; ks < 4; ++ks) {
+			if (c0 + 16 * ks >= b1) break;
+			h8 fa[2], fb[2];
+#pragma unroll
+			for (int a = 0; a < 2; ++a) fa[a] = ff_frag_tr(s_d, 16 * ks, wo + 32 * a, lane);
+#pragma unroll
+			for (int b = 0; b < 2; ++b) fb[b] = ff_frag_tr(s_x, 16 * ks, wi + 32 * b, lane);
+#pragma unroll
+			for (int a = 0; a < 2; ++a)
+#pragma unroll
+				for (int b = 0; b < 2; ++b)
+					if (on[a][b]) acc[a][b] = ff_mfma(fa[a], fb[b], acc[a][b]);
+		}
+	}
+	float* prow = G.partial + (size_t)blockIdx.y * G.ld_partial + G.off;
+#pragma unroll
+	for (int a = 0; a < 2; ++a)
+#pragma unroll
+		for (int b = 0; b < 2; ++b)
+#pragma unroll
+			for (int i = 0; i < 16; ++i) {
+				const uint32_t o = o_blk + wo + 32 * a + ff_row(i, h), c = i_blk + wi + 32 * b + r;
+				if (o < G.O && c < G.I) prow[(size_t)o * G.I + c] = acc[a][b][i];
+			}
+}
+
+// Identity encoding (identity.h:44-70): X0[s][k] =(half)(in[s][k] scale + offset) for k < n_in, 1 for the padding
 // k < ld (the bias input of tcnn's padded encodings); mode 1: the backward-backward front, dL_ddLdinput scaled, padding 0
 __global__ void k_ff_input(uint32_t n, uint32_t n_in, uint32_t ld, const float* __restrict__ in, float scale, float offset, half_t* __restrict__ x,
                            uint32_t grad) {
@@ -240,8 +488,18 @@ __global__ void k_ff_out_delta(uint32_t n, uint32_t ld, uint32_t act, const half
 
 static uint32_t ff_blocks(uint64_t n, uint32_t per, uint32_t cap) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + per - 1) / per, cap)); }
 
+// a product takes k_ff_layer / k_ff_wgrad where its whole matrix fits them, and the wide kernels otherwise
+static bool ff_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+template <uint32_t MODE> static void ff_launch_wide(hipStream_t s, const FfLayer& L) {
+	const dim3 grid(ff_blocks(L.n, 256, FF_WIDE_LAYER_BLOCKS), (L.O + FFW_OT - 1) / FFW_OT);
+	if (L.trans) k_ff_layer_wide<MODE, true><<<grid, 256, 0, s>>>(L);
+	else k_ff_layer_wide<MODE, false><<<grid, 256, 0, s>>>(L);
+}
 void launch_ff_layer(hipStream_t s, const FfLayer& L) {
-	if (L.K % 16 || L.K == 0 || L.O == 0 || L.O > 128) throw std::runtime_error("ff layer: K must be a multiple of 16, 1 <= O <= 128");
+	if (L.K % 16 || L.K == 0 || L.O == 0 || L.O > 512 || L.K > 512) throw std::runtime_error("ff layer: K must be a multiple of 16, 1 <= O, K <= 512");
+	const bool wide = L.O > 128 || L.K > 128;
+	if (wide && (L.O % 8 || L.ldi % 8 || !ff_al16(L.W) || !ff_al16(L.in)))
+		throw std::runtime_error("ff layer: a matrix above 128 rows or columns needs O and the input stride multiples of 8 and 16-byte aligned tensors");
 	if (L.mode > FF_MODE_OUT_CURV || (!L.in && L.mode != FF_MODE_CURV)) throw std::runtime_error("ff layer: unknown mode / null input");
 	if (L.mode != FF_MODE_ACT && L.mode != FF_MODE_F32) {  // the vector epilogue: whole groups of four rows, 8-byte aligned rows
 		const auto al8 = [](const void* p) { return ((uintptr_t)p & 7) == 0; };
@@ -249,6 +507,16 @@ void launch_ff_layer(hipStream_t s, const FfLayer& L) {
 			throw std::runtime_error("ff layer: the derivative epilogues need O and the row strides multiples of 4 and 8-byte aligned tensors");
 		if ((L.mode == FF_MODE_DACT && !L.out) || (L.mode == FF_MODE_CURV && (!L.out || !L.p || !L.t)) || (L.mode == FF_MODE_OUT_CURV && (!L.out2 || !L.t)))
 			throw std::runtime_error("ff layer: a tensor of the epilogue is null");
+	}
+	if (wide) {
+		switch (L.mode) {
+		case FF_MODE_ACT: ff_launch_wide<FF_MODE_ACT>(s, L); break;
+		case FF_MODE_DACT: ff_launch_wide<FF_MODE_DACT>(s, L); break;
+		case FF_MODE_F32: ff_launch_wide<FF_MODE_F32>(s, L); break;
+		case FF_MODE_CURV: ff_launch_wide<FF_MODE_CURV>(s, L); break;
+		default: ff_launch_wide<FF_MODE_OUT_CURV>(s, L); break;
+		}
+		return;
 	}
 	const size_t smem = (size_t)((L.O + 31) / 32 * 32) * (L.K + 8) * sizeof(half_t);
 	const uint32_t blocks = ff_blocks(L.n, 128, 1024);
@@ -260,10 +528,19 @@ void launch_ff_layer(hipStream_t s, const FfLayer& L) {
 	default: k_ff_layer<FF_MODE_OUT_CURV><<<blocks, 256, smem, s>>>(L); break;
 	}
 }
-uint32_t ff_wgrad_blocks(uint32_t n) { return ff_blocks(n, 1024, 512); }
+// wide: at most FF_WIDE_SLICES sample slices of at least 256 samples, so a wide network's partial rows do not grow with n
+uint32_t ff_wgrad_blocks(uint32_t n, bool wide) { return wide ? ff_blocks(n, 256, FF_WIDE_SLICES) : ff_blocks(n, 1024, 512); }
 void launch_ff_wgrad(hipStream_t s, const FfWgrad& G) {
-	if (G.O == 0 || G.I == 0 || G.O > 128 || G.I > 128) throw std::runtime_error("ff wgrad: 1..128 rows and columns");
+	if (G.O == 0 || G.I == 0 || G.O > 512 || G.I > 512) throw std::runtime_error("ff wgrad: 1..512 rows and columns");
 	if (!G.D2 != !G.X2) throw std::runtime_error("ff wgrad: the second product needs both of its factors");
+	if (G.O > 128 || G.I > 128) {
+		if (G.O % 8 || G.I % 8 || G.ldd % 8 || G.ldx % 8 || !ff_al16(G.D) || !ff_al16(G.X) || !ff_al16(G.D2) || !ff_al16(G.X2))
+			throw std::runtime_error("ff wgrad: a matrix above 128 rows or columns needs its sizes and strides multiples of 8 and 16-byte aligned tensors");
+		const uint32_t slices = ff_wgrad_blocks(G.n, true);
+		const dim3 grid(((G.O + FFW_OT - 1) / FFW_OT) * ((G.I + FFW_OT - 1) / FFW_OT), slices);
+		k_ff_wgrad_wide<<<grid, 256, 0, s>>>(G, (G.n + slices - 1) / slices);
+		return;
+	}
 	const size_t smem = (size_t)((G.O + 31) / 32 * 32 + (G.I + 31) / 32 * 32) * 40 * sizeof(half_t);
 	k_ff_wgrad<<<ff_wgrad_blocks(G.n), 256, smem, s>>>(G);
 }

@@ -287,7 +287,9 @@ struct FfWgrad {
 	const half_t* D2; const half_t* X2;                // a second product D2^T X2 (same shapes and strides) into the same sums; null: none
 };
 void launch_ff_layer(hipStream_t s, const FfLayer& L);
-uint32_t ff_wgrad_blocks(uint32_t n);  // blocks (= partial rows) of launch_ff_wgrad for n samples
+// partial rows of launch_ff_wgrad for n samples: its blocks, or (wide: a matrix above 128 rows or columns, as every matrix
+// of a network wider than 128 is) its sample slices
+uint32_t ff_wgrad_blocks(uint32_t n, bool wide = false);
 void launch_ff_wgrad(hipStream_t s, const FfWgrad& G);
 void launch_ff_input(hipStream_t s, uint32_t n, uint32_t n_in, uint32_t ld, const float* in, float scale, float offset, half_t* x, bool grad);
 void launch_ff_out_delta(hipStream_t s, uint32_t n, uint32_t ld, uint32_t act, const half_t* dL, const half_t* out, half_t* d);

@@ -3255,6 +3255,10 @@ struct FfNet {
 	std::vector<uint32_t> off, rows, cols;
 	uint32_t P = 0;
 	bool exact = false;  // "second_order": "exact": backward_backward_input carries the act'' terms
+	bool cutlass = false;  // a CutlassMLP width that FullyFusedMLP does not have (the hyperparams echo the otype)
+	// above 128 every matrix has more than 128 rows or columns and takes ffmlp.hip's wide kernels
+	bool wide() const { return W > 128; }
+	uint32_t wgrad_rows(uint32_t n) const { return ff_wgrad_blocks(n, wide()); }  // partial rows of a batch's weight gradients
 	// where act'' != 0: the hidden activation / any of the two (only then does an exact module differ from a default one)
 	bool hidden_curved() const { return act != FF_RELU && act != FF_NONE; }
 	bool curved() const { return exact && (hidden_curved() || out_act != FF_NONE); }
@@ -3278,15 +3282,23 @@ struct FfNet {
 	}
 };
 // A FullyFusedMLP from its config (fully_fused_mlp.cu:816-879): n_neurons 16 / 32 / 64 / 128, n_hidden_layers >= 1, input and
-// output padded to multiples of 16 (cpp::Module::n_output_dims = the padded output width). Host only.
+// output padded to multiples of 16 (cpp::Module::n_output_dims = the padded output width). A CutlassMLP (cutlass_mlp.cu:
+// 104-150) has the same matrices, padding and initialisation at any width: n_neurons a multiple of 16 up to 512. Host only.
 FfNet ff_from_json(const JsonValue& j, uint32_t n_input_dims, uint32_t n_output_dims) {
 	const std::string ot = j.string("otype", "FullyFusedMLP");
 	if (ot != "FullyFusedMLP" && ot != "MegakernelMLP" && ot != "CutlassMLP")
 		throw std::runtime_error("only FullyFusedMLP networks are implemented on gfx950");
 	FfNet f;
 	f.W = (uint32_t)j.number("n_neurons", 64);
-	if (f.W != 16 && f.W != 32 && f.W != 64 && f.W != 128)
+	const double nn = j.number("n_neurons", 64);
+	const bool ff_width = f.W == 16 || f.W == 32 || f.W == 64 || f.W == 128;
+	if (ot == "CutlassMLP") {
+		if (!(nn >= 16 && nn <= 512) || nn != (double)f.W || f.W % 16)
+			throw std::runtime_error("CutlassMLP: n_neurons must be a multiple of 16 from 16 to 512 on gfx950, but got " + fmt_float((float)nn));
+		f.cutlass = !ff_width;
+	} else if (!ff_width) {
 		throw std::runtime_error("FullyFusedMLP only supports 16, 32, 64, and 128 neurons, but got " + std::to_string(f.W));
+	}
 	const double nh = j.number("n_hidden_layers", 1);
 	if (nh < 1 || nh > 32) throw std::runtime_error("FullyFusedMLP requires at least 1 hidden layer (3 layers in total).");
 	f.N = (uint32_t)nh;
@@ -3304,7 +3316,7 @@ FfNet ff_from_json(const JsonValue& j, uint32_t n_input_dims, uint32_t n_output_
 }
 std::string ff_hyper(const FfNet& f) {
 	static const char* an[6] = {"None", "ReLU", "Exponential", "Sigmoid", "Squareplus", "Softplus"};
-	return "{\"otype\": \"FullyFusedMLP\", \"n_neurons\": " + std::to_string(f.W) + ", \"n_hidden_layers\": " + std::to_string(f.N) +
+	return std::string("{\"otype\": \"") + (f.cutlass ? "CutlassMLP" : "FullyFusedMLP") + "\", \"n_neurons\": " + std::to_string(f.W) + ", \"n_hidden_layers\": " + std::to_string(f.N) +
 	       ", \"activation\": \"" + an[f.act] + "\", \"output_activation\": \"" + an[f.out_act] + "\"" +
 	       (f.exact ? ", \"second_order\": \"exact\"" : "") + "}";
 }
@@ -3321,7 +3333,7 @@ struct FfWork {
 		front.alloc((size_t)capacity * (f.in_pad + (size_t)f.N * f.W));
 		const uint32_t dmax = std::max(std::max(f.W, f.out_pad), f.in_pad);
 		d[0].alloc((size_t)capacity * dmax); d[1].alloc((size_t)capacity * dmax);
-		partial.alloc((size_t)ff_wgrad_blocks(capacity) * f.P);
+		partial.alloc((size_t)f.wgrad_rows(capacity) * f.P);
 		dummy.alloc(4);
 		if (!f.curved()) return;
 		e[0].alloc((size_t)capacity * dmax); e[1].alloc((size_t)capacity * dmax);
@@ -3967,7 +3979,7 @@ struct NeusModule {
 	// the epilogue of a call with parameter gradients: the network's weight gradients from its partials, then g into dL_dparams
 	void finish_grad(float* g, uint32_t n, void* dL_dparams, int mode, hipStream_t s) {
 		if (!g) return;
-		if (net()) ff_reduce(ff, fw, s, ff_wgrad_blocks(n), g);
+		if (net()) ff_reduce(ff, fw, s, ff.wgrad_rows(n), g);
 		if (grad_fp16) launch_grad_to_half(s, (uint32_t)P, gtmp.p, (half_t*)dL_dparams, mode == NEUS_GRADIENT_ACCUMULATE);
 		else if (mode == NEUS_GRADIENT_ACCUMULATE) launch_add_f32(s, (uint32_t)P, gtmp.p, (float*)dL_dparams);
 	}
@@ -4095,7 +4107,7 @@ int neus_module_create_encoding(uint32_t n_input_dims, const char* encoding_json
 }
 
 // create_network_with_input_encoding (cpp_api.h:108; network_with_input_encoding.h): any encoding of create_encoding, or
-// Identity with scale / offset (any input width), in front of a FullyFusedMLP of any depth, width 16 / 32 / 64 / 128 and
+// Identity with scale / offset (any input width), in front of a FullyFusedMLP (or CutlassMLP: ff_from_json) of any depth, width and
 // activations. HashGrid -> one hidden ReLU layer -> linear network of width 16 / 64 runs on the fused k_dnet kernel.
 int neus_module_create_network_with_input_encoding(uint32_t n_input_dims, uint32_t n_output_dims, const char* encoding_json,
                                                    const char* network_json, uint32_t batch_capacity, NeusModule** out) {

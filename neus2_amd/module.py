@@ -71,7 +71,8 @@ class Module:
     def create_network(cls, n_input_dims, n_output_dims, network, batch_capacity=1 << 18):
         """tcnn create_network (cpp_api.h:109; cpp_api.cu:170-172): NetworkWithInputEncoding with an Identity encoding and
         a FullyFusedMLP (`network`: {"otype": "FullyFusedMLP", "n_neurons", "n_hidden_layers", "activation",
-        "output_activation"})."""
+        "output_activation"}; n_neurons 16, 32, 64 or 128) or a CutlassMLP ("otype": "CutlassMLP": n_neurons any multiple of
+        16 from 16 to 512, the same layout and initialisation; above 128 on ffmlp.hip's wide MFMA kernels)."""
         text = network if isinstance(network, str) else json.dumps(network)
         h = C.c_void_p()
         check(lib().neus_module_create_network(C.c_uint32(n_input_dims), C.c_uint32(n_output_dims), text.encode(),
@@ -93,7 +94,8 @@ class Module:
         grid create_encoding accepts, n_input_dims 2 - 4, encoded width F L <= 128, zero-padded to 16),
         Identity ({"scale", "offset"}, identity.h), Frequency ({"n_frequencies": 1..16}), SphericalHarmonics ({"degree": 1..8},
         3 dims) or Composite ({"nested": [{"n_dims_to_encode", ...}, ...]} of the last three; encoded width <= 128, padded to
-        16 with ones), `network` a FullyFusedMLP of any depth / width (16..128) / activation.
+        16 with ones), `network` a FullyFusedMLP of any depth / width (16, 32, 64, 128) / activation, or a CutlassMLP of any width that is
+        a multiple of 16 up to 512.
         Params [network matrices in order | grid] (network first, as NetworkWithInputEncoding's set_params_impl,
         network_with_input_encoding.h:262-270); output [n, padded n_output_dims] fp16; the grid's output is zero-padded to
         a multiple of 16 (grid.h:1540-1550). HashGrid -> one hidden ReLU layer with a linear output of <= 16 dims runs as

@@ -18,6 +18,10 @@ Dense / Tiled, "interpolation" Linear / Smoothstep; with Smoothstep the double b
 derivatives), and the parameter-free Identity, Frequency, SphericalHarmonics and Composite (of those three), whose `params`
 is an empty Parameter.
 
+Networks: "otype" FullyFusedMLP (n_neurons 16, 32, 64 or 128) or CutlassMLP (n_neurons any multiple of 16 from 16 to 512:
+the way to a 256- or 512-wide network, as in tiny-cuda-nn), 1 to 32 hidden layers, up to 128 input and output dims; the
+config is passed through to the native module, which validates it.
+
 Two autograd Functions talk to a small backend object (`NativeBackend` over module.Module by default):
     n_params, n_input_dims, n_output_dims (the backend's, possibly padded, output width), param_dtype, output_dtype,
     supports_double_backward, batch_capacity (None: unlimited), with_capacity(n), initialize_params(seed),
@@ -233,7 +237,8 @@ class Encoding(Module):
 
 
 class Network(Module):
-    """Network(n_input_dims, n_output_dims, network_config, seed=1337): a FullyFusedMLP on the raw input."""
+    """Network(n_input_dims, n_output_dims, network_config, seed=1337): a FullyFusedMLP (width 16 / 32 / 64 / 128) or a
+    CutlassMLP (any multiple of 16 up to 512) on the raw input."""
 
     def __init__(self, n_input_dims, n_output_dims, network_config, seed=1337):
         self.network_config = dict(_text(network_config), gradient_precision="fp32", second_order="exact")
