@@ -466,7 +466,8 @@ int neus_debug_host_group_allreduce(NeusHostGroup* group, void* host, uint64_t n
  *                                encoding (inputs padded to 16 with ones) in front of a FullyFusedMLP (n_neurons 16 / 32 /
  *                                64 / 128) or a CutlassMLP (n_neurons a multiple of 16 from 16 to 512; the same layout),
  *                                n_hidden_layers >= 1, activation / output_activation None, ReLU, Exponential,
- *                                Sigmoid, Squareplus, Softplus; input [n][n_input_dims] f32, output [n][padded out] fp16,
+ *                                Sigmoid, Squareplus, Softplus, and for a CutlassMLP's hidden activation also Sine (a SIREN;
+ *                                the forward's context keeps cos z); input [n][n_input_dims] f32, output [n][padded out] fp16,
  *                                params [W x in_pad | (N - 1) x W x W | out_pad x W] fp16 (fully_fused_mlp.cu:816-879);
  *                                n must be a multiple of 128 (fully_fused_mlp.cu:779-781).
  *   neus_module_create_encoding  create_encoding (HashGrid, grid.h): input [n][3] f32; output layout from the config's

@@ -14,7 +14,9 @@
 //
 // A CutlassMLP (my_tcnn src/cutlass_mlp.cu) is the same network at any width up to 512. Matrices of at most 128 x 128 take
 // the two kernels above; larger ones take k_ff_layer_wide / k_ff_wgrad_wide below, which tile the output rows over the
-// grid and stage the reduction axis in chunks, with the same arithmetic per element.
+// grid and stage the reduction axis in chunks, with the same arithmetic per element. A CutlassMLP also takes the Sine
+// activation (cutlass_mlp.cu:102), the one whose derivative the stored post-activation value does not give: its forward keeps
+// cos z beside sin z, and both layer kernels have Sine instantiations of their own (ff_sine_epilogue).
 #include "kernels.h"
 #include <algorithm>
 #include <stdexcept>
@@ -59,6 +61,19 @@ __device__ __forceinline__ float ff_d2act(uint32_t act, float y) {
 	default: return 0.f;
 	}
 }
+// sin and cos of an fp16 value x (exact in fp32, |x| <= 65504) for FF_SINE. With 1 / (2 pi) in two floats and r the whole
+// turns, the fraction of a turn is x hi - r from one fma (the exact product minus an integer, rounded once: 2^-25 turns)
+// plus x lo, so it is good to about 2^-24 turns at any magnitude the argument can have, where a single fp32 product is off
+// by up to 5e-4 turns at 65504 (3e-3 rad, six fp16 ulps of the result). Every multiply-add is written as an fma: a form
+// that corrects a rounded product by its error counts the error twice once the compiler contracts the product. v_sin_f32 /
+// v_cos_f32 take turns and are good to about 2^-17 absolute, a thirtieth of the fp16 rounding that follows.
+__device__ __forceinline__ void ff_sincos(float x, float& sn, float& cs) {
+	constexpr float INV_2PI_HI = 0x1.45f306p-3f, INV_2PI_LO = 0x1.b9391p-28f;  // 1 / (2 pi) = hi + lo to 2^-52
+	const float r = __builtin_rintf(x * INV_2PI_HI);
+	const float f = __builtin_fmaf(x, INV_2PI_LO, __builtin_fmaf(x, INV_2PI_HI, -r));
+	sn = __builtin_amdgcn_sinf(f);
+	cs = __builtin_amdgcn_cosf(f);
+}
 // four consecutive fp16 of a row as floats / back (accumulator registers 4j .. 4j + 3 are four consecutive output rows)
 __device__ __forceinline__ void ff_load4(const half_t* p, float v[4]) {
 	const h4 x = *(const h4*)p;
@@ -83,7 +98,49 @@ __device__ __forceinline__ void ff_store4(half_t* p, const float v[4]) {
 //   mode FF_MODE_OUT_CURV: out = d (fp16 sum) (skipped when null), out2 = c (fp16 sum) t[s][o]: the output layer's
 //                          dL_ddLdoutput and curvature adjoint from the front carried through the last matrix
 // One instantiation per mode: the MFMA body is shared, and no epilogue holds another's registers.
-template <uint32_t MODE> __global__ void __launch_bounds__(256) k_ff_layer(FfLayer L) {
+//
+// FF_SINE (SINE instantiations of modes ACT, DACT and CURV, for both kernels; O a multiple of 4, vector accesses throughout):
+// act' = cos z is not a function of the stored sin z, so
+//   mode ACT : out = sin(fp16 sum), out2 (when given) = cos(fp16 sum), the pair from one reduction of the argument
+//   mode DACT: out = (fp16 sum) auxc[s][o], out2 as above (aux is not read)
+//   mode CURV: out = -aux[s][o] p[s][o] t[s][o] + auxc[s][o] (fp16 sum)       (act'' = -sin z = -aux)
+// on one sample's 4 row tiles from row o_blk on. The other activations' instantiations do not contain any of this.
+template <uint32_t MODE>
+__device__ __forceinline__ void ff_sine_epilogue(const FfLayer& L, const f16v (&acc)[4], uint32_t s, uint32_t o_blk, uint32_t MT, int h) {
+	static_assert(MODE == FF_MODE_ACT || MODE == FF_MODE_DACT || MODE == FF_MODE_CURV, "Sine is a hidden activation");
+#pragma unroll
+	for (int mt = 0; mt < 4; ++mt) {
+		if ((uint32_t)mt >= MT) break;
+#pragma unroll
+		for (int j = 0; j < 4; ++j) {
+			const uint32_t o0 = o_blk + 32 * mt + ff_row(4 * j, h);
+			if (o0 >= L.O) continue;
+			const size_t at = (size_t)s * L.ldo + o0;
+			float x[4], r0[4], r1[4], c[4], y[4], pv[4], tv[4];
+			if constexpr (MODE != FF_MODE_ACT) ff_load4(L.auxc + (size_t)s * L.ldx + o0, c);
+			if constexpr (MODE == FF_MODE_CURV) {
+				ff_load4(L.aux + (size_t)s * L.ldx + o0, y);
+				ff_load4(L.p + at, pv);
+				ff_load4(L.t + at, tv);
+			}
+#pragma unroll
+			for (int k = 0; k < 4; ++k) {
+				x[k] = (float)(half_t)acc[mt][4 * j + k];
+				if constexpr (MODE == FF_MODE_ACT) {
+					ff_sincos(x[k], r0[k], r1[k]);
+				} else {
+					r0[k] = x[k] * c[k];
+					if constexpr (MODE == FF_MODE_CURV) r0[k] = -y[k] * pv[k] * tv[k] + r0[k];
+					r1[k] = x[k];
+				}
+			}
+			ff_store4(L.out + at, r0);
+			if constexpr (MODE != FF_MODE_CURV) if (L.out2) ff_store4(L.out2 + at, r1);
+		}
+	}
+}
+
+template <uint32_t MODE, bool SINE = false> __global__ void __launch_bounds__(256) k_ff_layer(FfLayer L) {
 	extern __shared__ half_t s_w[];
 	const uint32_t Op = (L.O + 31) / 32 * 32, lda = L.K + 8;
 	// stage A [Op][K] (+ 8 halves of row padding); rows >= O are zero
@@ -116,7 +173,9 @@ template <uint32_t MODE> __global__ void __launch_bounds__(256) k_ff_layer(FfLay
 			}
 		}
 		if (!valid) continue;
-		if constexpr (MODE != FF_MODE_ACT && MODE != FF_MODE_F32) {
+		if constexpr (SINE) {
+			ff_sine_epilogue<MODE>(L, acc, s, 0, MT, h);
+		} else if constexpr (MODE != FF_MODE_ACT && MODE != FF_MODE_F32) {
 			// O is a multiple of 4 here (launch_ff_layer): registers 4j .. 4j + 3 are rows o0 .. o0 + 3, so every operand of the
 			// epilogue is one 8-byte load and every result one 8-byte store per lane
 #pragma unroll
@@ -343,7 +402,7 @@ __device__ __forceinline__ void ff_wide_epilogue(const FfLayer& L, const f16v (&
 // per lane; W^T of W [K][O] (TRANS) as the [k][row] image of its rows as they lie in memory, read transposed. A wave's
 // input fragments of a chunk are loaded before the chunk is staged, and the matrix tile of the next chunk into registers
 // while the MFMAs run on the current one.
-template <uint32_t MODE, bool TRANS> __global__ void __launch_bounds__(256) k_ff_layer_wide(FfLayer L) {
+template <uint32_t MODE, bool TRANS, bool SINE = false> __global__ void __launch_bounds__(256) k_ff_layer_wide(FfLayer L) {
 	__shared__ __attribute__((aligned(16))) half_t s_a[FFW_IMG];
 	const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5, wv = threadIdx.x >> 6;
 	const uint32_t o_blk = blockIdx.y * FFW_OT;
@@ -395,8 +454,13 @@ template <uint32_t MODE, bool TRANS> __global__ void __launch_bounds__(256) k_ff
 				}
 			}
 		}
-		if (sb + r < L.n) ff_wide_epilogue<MODE>(L, acc[0], sb + r, o_blk, MT, h);
-		if (sb + 32 + r < L.n) ff_wide_epilogue<MODE>(L, acc[1], sb + 32 + r, o_blk, MT, h);
+		if constexpr (SINE) {
+			if (sb + r < L.n) ff_sine_epilogue<MODE>(L, acc[0], sb + r, o_blk, MT, h);
+			if (sb + 32 + r < L.n) ff_sine_epilogue<MODE>(L, acc[1], sb + 32 + r, o_blk, MT, h);
+		} else {
+			if (sb + r < L.n) ff_wide_epilogue<MODE>(L, acc[0], sb + r, o_blk, MT, h);
+			if (sb + 32 + r < L.n) ff_wide_epilogue<MODE>(L, acc[1], sb + 32 + r, o_blk, MT, h);
+		}
 	}
 }
 
@@ -490,10 +554,14 @@ static uint32_t ff_blocks(uint64_t n, uint32_t per, uint32_t cap) { return (uint
 
 // a product takes k_ff_layer / k_ff_wgrad where its whole matrix fits them, and the wide kernels otherwise
 static bool ff_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-template <uint32_t MODE> static void ff_launch_wide(hipStream_t s, const FfLayer& L) {
+template <uint32_t MODE, bool SINE = false> static void ff_launch_wide(hipStream_t s, const FfLayer& L) {
 	const dim3 grid(ff_blocks(L.n, 256, FF_WIDE_LAYER_BLOCKS), (L.O + FFW_OT - 1) / FFW_OT);
-	if (L.trans) k_ff_layer_wide<MODE, true><<<grid, 256, 0, s>>>(L);
-	else k_ff_layer_wide<MODE, false><<<grid, 256, 0, s>>>(L);
+	if (L.trans) k_ff_layer_wide<MODE, true, SINE><<<grid, 256, 0, s>>>(L);
+	else k_ff_layer_wide<MODE, false, SINE><<<grid, 256, 0, s>>>(L);
+}
+template <uint32_t MODE> static void ff_launch_sine(hipStream_t s, const FfLayer& L, bool wide, uint32_t blocks, size_t smem) {
+	if (wide) ff_launch_wide<MODE, true>(s, L);
+	else k_ff_layer<MODE, true><<<blocks, 256, smem, s>>>(L);
 }
 void launch_ff_layer(hipStream_t s, const FfLayer& L) {
 	if (L.K % 16 || L.K == 0 || L.O == 0 || L.O > 512 || L.K > 512) throw std::runtime_error("ff layer: K must be a multiple of 16, 1 <= O, K <= 512");
@@ -501,12 +569,26 @@ void launch_ff_layer(hipStream_t s, const FfLayer& L) {
 	if (wide && (L.O % 8 || L.ldi % 8 || !ff_al16(L.W) || !ff_al16(L.in)))
 		throw std::runtime_error("ff layer: a matrix above 128 rows or columns needs O and the input stride multiples of 8 and 16-byte aligned tensors");
 	if (L.mode > FF_MODE_OUT_CURV || (!L.in && L.mode != FF_MODE_CURV)) throw std::runtime_error("ff layer: unknown mode / null input");
+	const auto al8 = [](const void* p) { return ((uintptr_t)p & 7) == 0; };
 	if (L.mode != FF_MODE_ACT && L.mode != FF_MODE_F32) {  // the vector epilogue: whole groups of four rows, 8-byte aligned rows
-		const auto al8 = [](const void* p) { return ((uintptr_t)p & 7) == 0; };
 		if (L.O % 4 || L.ldo % 4 || L.ldx % 4 || !L.aux || !al8(L.aux) || !al8(L.out) || !al8(L.out2) || !al8(L.p) || !al8(L.t))
 			throw std::runtime_error("ff layer: the derivative epilogues need O and the row strides multiples of 4 and 8-byte aligned tensors");
 		if ((L.mode == FF_MODE_DACT && !L.out) || (L.mode == FF_MODE_CURV && (!L.out || !L.p || !L.t)) || (L.mode == FF_MODE_OUT_CURV && (!L.out2 || !L.t)))
 			throw std::runtime_error("ff layer: a tensor of the epilogue is null");
+	}
+	const size_t smem = (size_t)((L.O + 31) / 32 * 32) * (L.K + 8) * sizeof(half_t);
+	const uint32_t blocks = ff_blocks(L.n, 128, 1024);
+	if (L.act == FF_SINE) {  // its own instantiations: a hidden activation, so the modes that hidden layers run
+		const bool dv = L.mode != FF_MODE_ACT;
+		if (L.mode != FF_MODE_ACT && L.mode != FF_MODE_DACT && L.mode != FF_MODE_CURV) throw std::runtime_error("ff layer: Sine is a hidden activation (modes ACT, DACT, CURV)");
+		if (L.O % 4 || L.ldo % 4 || !L.out || !al8(L.out) || !al8(L.out2) || (dv && (!L.auxc || !al8(L.auxc))))
+			throw std::runtime_error("ff layer: Sine needs O and the row stride multiples of 4, 8-byte aligned tensors and, for its derivative, the forward's cos values");
+		switch (L.mode) {
+		case FF_MODE_ACT: ff_launch_sine<FF_MODE_ACT>(s, L, wide, blocks, smem); break;
+		case FF_MODE_DACT: ff_launch_sine<FF_MODE_DACT>(s, L, wide, blocks, smem); break;
+		default: ff_launch_sine<FF_MODE_CURV>(s, L, wide, blocks, smem); break;
+		}
+		return;
 	}
 	if (wide) {
 		switch (L.mode) {
@@ -518,8 +600,6 @@ void launch_ff_layer(hipStream_t s, const FfLayer& L) {
 		}
 		return;
 	}
-	const size_t smem = (size_t)((L.O + 31) / 32 * 32) * (L.K + 8) * sizeof(half_t);
-	const uint32_t blocks = ff_blocks(L.n, 128, 1024);
 	switch (L.mode) {
 	case FF_MODE_ACT: k_ff_layer<FF_MODE_ACT><<<blocks, 256, smem, s>>>(L); break;
 	case FF_MODE_DACT: k_ff_layer<FF_MODE_DACT><<<blocks, 256, smem, s>>>(L); break;

@@ -266,7 +266,9 @@ bool dnet_supported(uint32_t L, uint32_t W);
 uint32_t dnet_blocks(uint32_t n);  // the grid of launch_dnet (= the partial rows of modes 1 and 2)
 void launch_dnet(hipStream_t s, uint32_t L, uint32_t W, int mode /* 0 fwd, 1 bwd, 2 bwd-bwd */, uint32_t n, const DNetLaunch& d);
 // ffmlp.hip: tcnn FullyFusedMLP behind the Identity encoding (cpp_api.cu:170-172, the network of create_network)
-enum : uint32_t { FF_NONE = 0, FF_RELU = 1, FF_EXP = 2, FF_SIGMOID = 3, FF_SQUAREPLUS = 4, FF_SOFTPLUS = 5 };
+// FF_SINE (a CutlassMLP's hidden activation only, cutlass_mlp.cu:102): its derivative is not a function of the stored sin z, so
+// the forward keeps cos z beside it (FfLayer::out2 / auxc) and the kernels have instantiations of their own for it
+enum : uint32_t { FF_NONE = 0, FF_RELU = 1, FF_EXP = 2, FF_SIGMOID = 3, FF_SQUAREPLUS = 4, FF_SOFTPLUS = 5, FF_SINE = 6 };
 // k_ff_layer's epilogues. The last two carry the curvature (act'') terms of the exact double backward.
 enum : uint32_t { FF_MODE_ACT = 0, FF_MODE_DACT = 1, FF_MODE_F32 = 2, FF_MODE_CURV = 3, FF_MODE_OUT_CURV = 4 };
 struct FfLayer {
@@ -276,8 +278,10 @@ struct FfLayer {
 	float out_scale = 1.f;                             // mode F32: the fp16-rounded sum times this (an Identity encoding's scale)
 	const half_t* aux; uint32_t ldx;                   // modes DACT, CURV, OUT_CURV: forward post-activation values [n][ldx]
 	uint32_t mode, act, n;
-	half_t* out2;                                      // [n][ldo]: mode DACT: the fp16 sum itself (null: not kept); mode OUT_CURV: see ffmlp.hip
+	half_t* out2;                                      // [n][ldo]: mode DACT: the fp16 sum itself (null: not kept); mode OUT_CURV: see ffmlp.hip;
+	                                                   // mode ACT with FF_SINE: cos of the fp16 sum (null: not kept)
 	const half_t* p; const half_t* t;                  // [n][ldo]: mode CURV: both factors of the act'' term; mode OUT_CURV: t
+	const half_t* auxc;                                // FF_SINE, modes DACT and CURV: the forward's kept cos values [n][ldx], beside aux
 };
 struct FfWgrad {
 	const half_t* D; uint32_t ldd, O;                  // [n][ldd] deltas

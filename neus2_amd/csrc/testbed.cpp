@@ -3244,6 +3244,7 @@ struct NeusContext {
 	Dev<float> dydx;     // HashGrid: dy/dx [6L][n] of the forward (prepare_input_gradients)
 	Dev<uint32_t> enc;   // HashGrid in front of a network: the forward's paired encoding [L][n] (k_dnet's input)
 	Dev<half_t> acts;    // FullyFusedMLP: the forward's input X0 [n][in_pad] and hidden outputs [N][n][W] (post-activation)
+	Dev<half_t> cosz;    // a Sine network only: cos of the hidden pre-activations [N][n][W], the derivative sin z does not give
 };
 
 namespace {
@@ -3255,12 +3256,13 @@ struct FfNet {
 	std::vector<uint32_t> off, rows, cols;
 	uint32_t P = 0;
 	bool exact = false;  // "second_order": "exact": backward_backward_input carries the act'' terms
-	bool cutlass = false;  // a CutlassMLP width that FullyFusedMLP does not have (the hyperparams echo the otype)
+	bool cutlass = false;  // a CutlassMLP that is no FullyFusedMLP: another width, or Sine (the hyperparams echo the otype)
 	// above 128 every matrix has more than 128 rows or columns and takes ffmlp.hip's wide kernels
 	bool wide() const { return W > 128; }
 	uint32_t wgrad_rows(uint32_t n) const { return ff_wgrad_blocks(n, wide()); }  // partial rows of a batch's weight gradients
 	// where act'' != 0: the hidden activation / any of the two (only then does an exact module differ from a default one)
 	bool hidden_curved() const { return act != FF_RELU && act != FF_NONE; }
+	bool sine() const { return act == FF_SINE; }  // the forward keeps cos z in the context (NeusContext::cosz)
 	bool curved() const { return exact && (hidden_curved() || out_act != FF_NONE); }
 	void build() {
 		off.clear(); rows.clear(); cols.clear(); P = 0;
@@ -3270,7 +3272,10 @@ struct FfNet {
 		}
 	}
 	size_t acts_halves(uint32_t n) const { return (size_t)n * (in_pad + (size_t)N * W); }
-	static uint32_t activation(const std::string& s) {
+	// `sine`: a CutlassMLP's hidden activation (cutlass_mlp.cu:102). tcnn's fully fused kernels keep only post-activations,
+	// and warp_activation_backward cannot recover cos z from sin z (common_device.h:196-200)
+	static uint32_t activation(const std::string& s, bool sine = false) {
+		if (s == "Sine" && sine) return FF_SINE;
 		if (s == "None") return FF_NONE;
 		if (s == "ReLU") return FF_RELU;
 		if (s == "Exponential") return FF_EXP;
@@ -3278,7 +3283,7 @@ struct FfNet {
 		if (s == "Squareplus") return FF_SQUAREPLUS;
 		if (s == "Softplus") return FF_SOFTPLUS;
 		throw std::runtime_error("FullyFusedMLP: activation '" + s + "' is not supported on gfx950 (None, ReLU, Exponential, Sigmoid, Squareplus, "
-		                         "Softplus; Sine has no backward in tcnn's fully fused MLP)");
+		                         "Softplus; Sine has no backward in tcnn's fully fused MLP: a CutlassMLP takes it as its hidden \"activation\")");
 	}
 };
 // A FullyFusedMLP from its config (fully_fused_mlp.cu:816-879): n_neurons 16 / 32 / 64 / 128, n_hidden_layers >= 1, input and
@@ -3306,7 +3311,11 @@ FfNet ff_from_json(const JsonValue& j, uint32_t n_input_dims, uint32_t n_output_
 	if (n_output_dims == 0 || n_output_dims > 128) throw std::runtime_error("FullyFusedMLP: 1..128 output dims on gfx950");
 	f.n_in = n_input_dims; f.in_pad = (n_input_dims + 15) / 16 * 16;
 	f.n_out = n_output_dims; f.out_pad = (n_output_dims + 15) / 16 * 16;
-	f.act = FfNet::activation(j.string("activation", "ReLU"));
+	f.act = FfNet::activation(j.string("activation", "ReLU"), ot == "CutlassMLP");
+	if (f.sine()) f.cutlass = true;  // at a FullyFusedMLP width too: that otype has no Sine
+	// a SIREN's output layer is linear, and the output-activation path would need a stored cos of its own
+	if (j.string("output_activation", "None") == "Sine")
+		throw std::runtime_error(ot + ": \"output_activation\": \"Sine\" is not supported on gfx950 (Sine is a CutlassMLP's hidden \"activation\" only)");
 	f.out_act = FfNet::activation(j.string("output_activation", "None"));
 	const std::string so = j.string("second_order", "tcnn");
 	if (so != "tcnn" && so != "exact") throw std::runtime_error("FullyFusedMLP: second_order must be tcnn or exact, but got '" + so + "'");
@@ -3315,7 +3324,7 @@ FfNet ff_from_json(const JsonValue& j, uint32_t n_input_dims, uint32_t n_output_
 	return f;
 }
 std::string ff_hyper(const FfNet& f) {
-	static const char* an[6] = {"None", "ReLU", "Exponential", "Sigmoid", "Squareplus", "Softplus"};
+	static const char* an[7] = {"None", "ReLU", "Exponential", "Sigmoid", "Squareplus", "Softplus", "Sine"};
 	return std::string("{\"otype\": \"") + (f.cutlass ? "CutlassMLP" : "FullyFusedMLP") + "\", \"n_neurons\": " + std::to_string(f.W) + ", \"n_hidden_layers\": " + std::to_string(f.N) +
 	       ", \"activation\": \"" + an[f.act] + "\", \"output_activation\": \"" + an[f.out_act] + "\"" +
 	       (f.exact ? ", \"second_order\": \"exact\"" : "") + "}";
@@ -3348,14 +3357,16 @@ struct FfSink { bool direct; float* dL_dinput; float scale; };
 // FullyFusedMLP passes (ffmlp.hip). acts: X0 [n][in_pad] then hidden l at n (in_pad + l W), each [n][W].
 const half_t* ff_mat(const FfNet& f, const void* params, uint32_t l) { return (const half_t*)params + f.off[l]; }
 half_t* ff_hidden(const FfNet& f, const half_t* acts, uint32_t n, uint32_t l) { return const_cast<half_t*>(acts) + (size_t)n * f.in_pad + (size_t)l * n * f.W; }
+// hidden layer l's cos values in a Sine network's kept buffer [N][n][W] (null for every other network)
+half_t* ff_kept_cos(const FfNet& f, const half_t* cosz, uint32_t n, uint32_t l) { return cosz ? const_cast<half_t*>(cosz) + (size_t)l * n * f.W : nullptr; }
 FfLayer ff_layer(const half_t* W, uint32_t O, uint32_t K, bool trans, const half_t* in, uint32_t ldi, uint32_t n) {
 	FfLayer L{};
 	L.W = W; L.O = O; L.K = K; L.trans = trans ? 1u : 0u; L.in = in; L.ldi = ldi; L.n = n;
 	return L;
 }
 // forward (mlp_fused_forward, fully_fused_mlp.cu:678-812) on the encoded rows X0 in acts: hidden layers act(W x), output
-// out_act(W_N h)
-void ff_forward(const FfNet& f, hipStream_t s, uint32_t n, const void* params, half_t* acts, half_t* output) {
+// out_act(W_N h). A Sine network with a context also writes cos(W x) [N][n][W] to cosz (null: inference, nothing kept)
+void ff_forward(const FfNet& f, hipStream_t s, uint32_t n, const void* params, half_t* acts, half_t* output, half_t* cosz = nullptr) {
 	const half_t* x = acts;
 	uint32_t ldx = f.in_pad;
 	for (uint32_t l = 0; l <= f.N; ++l) {
@@ -3364,6 +3375,7 @@ void ff_forward(const FfNet& f, hipStream_t s, uint32_t n, const void* params, h
 		L.act = l == f.N ? f.out_act : f.act;
 		L.out = l == f.N ? output : ff_hidden(f, acts, n, l);
 		L.ldo = l == f.N ? f.out_pad : f.W;
+		if (l < f.N) L.out2 = ff_kept_cos(f, cosz, n, l);
 		launch_ff_layer(s, L);
 		x = L.out; ldx = f.W;
 	}
@@ -3376,10 +3388,10 @@ void ff_output(const FfNet& f, hipStream_t s, uint32_t n, const void* params, co
 }
 // delta through layer l (l >= 1) to the input of layer l: act'(h_{l-1}) (W_l^T d); keep (when given): W_l^T d itself
 void ff_back_through(const FfNet& f, hipStream_t s, uint32_t n, const void* params, uint32_t l, const half_t* d, uint32_t ldd, const half_t* acts_fwd,
-                     half_t* out, half_t* keep = nullptr) {
+                     const half_t* cosz, half_t* out, half_t* keep = nullptr) {
 	FfLayer L = ff_layer(ff_mat(f, params, l), f.cols[l], f.rows[l], true, d, ldd, n);
 	L.mode = FF_MODE_DACT; L.act = f.act; L.out = out; L.out2 = keep; L.ldo = f.W;
-	L.aux = ff_hidden(f, acts_fwd, n, l - 1); L.ldx = f.W;
+	L.aux = ff_hidden(f, acts_fwd, n, l - 1); L.ldx = f.W; L.auxc = ff_kept_cos(f, cosz, n, l - 1);
 	launch_ff_layer(s, L);
 }
 void ff_wgrad(const FfNet& f, hipStream_t s, uint32_t n, uint32_t l, const half_t* d, uint32_t ldd, const half_t* x, uint32_t ldx, float* partial,
@@ -3393,8 +3405,8 @@ void ff_wgrad(const FfNet& f, hipStream_t s, uint32_t n, uint32_t l, const half_
 // through the hidden layers (activation derivative from the stored outputs), with wgrad dW = D^T x per layer into the
 // partials, and layer 0 into the sink: dL/dX0 as fp16 rows (returned; the delta ping-pong buffer), or dL/dinput = W_0^T D_0
 // through the Identity encoding's backward (identity.h:86-104: x scale)
-const half_t* ff_backward_chain(const FfNet& f, FfWork& w, hipStream_t s, uint32_t n, const void* params, const half_t* acts, const half_t* dL_doutput,
-                                const half_t* output, bool wgrad, const FfSink& sink) {
+const half_t* ff_backward_chain(const FfNet& f, FfWork& w, hipStream_t s, uint32_t n, const void* params, const half_t* acts, const half_t* cosz,
+                                const half_t* dL_doutput, const half_t* output, bool wgrad, const FfSink& sink) {
 	const half_t* d = dL_doutput;
 	int pp = 0;
 	if (f.out_act != FF_NONE) { launch_ff_out_delta(s, n, f.out_pad, f.out_act, d, output, w.d[0].p); d = w.d[0].p; pp = 1; }
@@ -3403,7 +3415,7 @@ const half_t* ff_backward_chain(const FfNet& f, FfWork& w, hipStream_t s, uint32
 		const half_t* x = l == 0 ? acts : ff_hidden(f, acts, n, l - 1);
 		if (wgrad) ff_wgrad(f, s, n, l, d, ldd, x, l == 0 ? f.in_pad : f.W, w.partial.p);
 		if (l > 0) {
-			ff_back_through(f, s, n, params, l, d, ldd, acts, w.d[pp].p);
+			ff_back_through(f, s, n, params, l, d, ldd, acts, cosz, w.d[pp].p);
 			d = w.d[pp].p; pp ^= 1; ldd = f.W;
 		} else if (!sink.direct) {
 			FfLayer L = ff_layer(ff_mat(f, params, 0), f.in_pad, f.W, true, d, ldd, n);
@@ -3431,8 +3443,9 @@ const half_t* ff_backward_chain(const FfNet& f, FfWork& w, hipStream_t s, uint32
 //   dW_{i-1} = d_i f_{i-1}^T + e_i h_{i-1}^T                                               (both products in one launch)
 // and q = W_0^T e_1 = d(dL_ddLdinput . dL/dx)/dX0 along the forward path leaves through the sink when want_q: behind the
 // Identity encoding x scale into dL_dinput, else as fp16 rows [n][in_pad] (returned) for the encoding's backward.
-const half_t* ff_bbi_chain(const FfNet& f, FfWork& w, hipStream_t s, uint32_t n, const void* params, const half_t* acts, const half_t* dL_doutput,
-                           bool wgrad, half_t* dL_ddLdoutput, bool want_q = false, const FfSink& sink = FfSink{false, nullptr, 1.f}) {
+// A Sine network takes act'(z_i) = cos z_i from the forward's kept cosz and act''(z_i) = -h_i from acts; nothing else differs.
+const half_t* ff_bbi_chain(const FfNet& f, FfWork& w, hipStream_t s, uint32_t n, const void* params, const half_t* acts, const half_t* cosz,
+                           const half_t* dL_doutput, bool wgrad, half_t* dL_ddLdoutput, bool want_q = false, const FfSink& sink = FfSink{false, nullptr, 1.f}) {
 	const bool cv = f.curved(), hc = cv && f.hidden_curved(), oc = cv && f.out_act != FF_NONE;
 	half_t* fr = w.front.p;
 	auto front = [&](uint32_t i) { return i == 0 ? fr : fr + (size_t)n * f.in_pad + (size_t)(i - 1) * n * f.W; };
@@ -3440,7 +3453,7 @@ const half_t* ff_bbi_chain(const FfNet& f, FfWork& w, hipStream_t s, uint32_t n,
 	for (uint32_t i = 1; i <= f.N; ++i) {
 		FfLayer L = ff_layer(ff_mat(f, params, i - 1), f.rows[i - 1], f.cols[i - 1], false, front(i - 1), i == 1 ? f.in_pad : f.W, n);
 		L.mode = FF_MODE_DACT; L.act = f.act; L.out = front(i); L.ldo = f.W;
-		L.aux = ff_hidden(f, acts, n, i - 1); L.ldx = f.W;
+		L.aux = ff_hidden(f, acts, n, i - 1); L.ldx = f.W; L.auxc = ff_kept_cos(f, cosz, n, i - 1);
 		if (hc) L.out2 = kept_p(i);
 		launch_ff_layer(s, L);
 	}
@@ -3466,14 +3479,14 @@ const half_t* ff_bbi_chain(const FfNet& f, FfWork& w, hipStream_t s, uint32_t n,
 	for (uint32_t l = f.N + 1; l-- > 0;) {
 		if (wgrad) ff_wgrad(f, s, n, l, b, ldb, front(l), l == 0 ? f.in_pad : f.W, w.partial.p, e, e ? (l == 0 ? acts : ff_hidden(f, acts, n, l - 1)) : nullptr);
 		if (l > 0) {
-			if (wgrad || hc) ff_back_through(f, s, n, params, l, b, ldb, acts, w.d[pp].p, hc ? w.t.p : nullptr);  // d_l, and t_l for the act'' term
+			if (wgrad || hc) ff_back_through(f, s, n, params, l, b, ldb, acts, cosz, w.d[pp].p, hc ? w.t.p : nullptr);  // d_l, and t_l for the act'' term
 			if (hc) {  // e_l; below a linear output there is no e_{l+1}: no product
 				FfLayer L = ff_layer(ff_mat(f, params, l), f.cols[l], f.rows[l], true, e, ldb, n);
 				L.mode = FF_MODE_CURV; L.act = f.act; L.out = w.e[ep].p; L.ldo = f.W;
-				L.aux = ff_hidden(f, acts, n, l - 1); L.ldx = f.W; L.p = kept_p(l); L.t = w.t.p;
+				L.aux = ff_hidden(f, acts, n, l - 1); L.ldx = f.W; L.auxc = ff_kept_cos(f, cosz, n, l - 1); L.p = kept_p(l); L.t = w.t.p;
 				launch_ff_layer(s, L);
 			} else if (e) {
-				ff_back_through(f, s, n, params, l, e, ldb, acts, w.e[ep].p);
+				ff_back_through(f, s, n, params, l, e, ldb, acts, cosz, w.e[ep].p);
 			}
 			if (hc || e) { e = w.e[ep].p; ep ^= 1; }
 			b = w.d[pp].p; pp ^= 1; ldb = f.W;
@@ -3994,7 +4007,7 @@ struct NeusModule {
 	}
 	// a context of this module's forward
 	bool ctx_ok(const NeusContext* ctx) const {
-		return (!enc.keeps_dydx() || ctx->dydx.p) && (!net() || ctx->acts.p) && (fused != Dnet || ctx->enc.p);
+		return (!enc.keeps_dydx() || ctx->dydx.p) && (!net() || (ctx->acts.p && (!ff.sine() || ctx->cosz.p))) && (fused != Dnet || ctx->enc.p);
 	}
 };
 
@@ -4191,7 +4204,18 @@ int neus_module_initialize_params(NeusModule* m, uint64_t seed, float* params_fu
 				for (uint32_t i = 0; i < out * in; ++i) h[off + i] = rnd.next_float() * 2.0f * scale - scale;
 				off += (size_t)out * in;
 			};
-			for (size_t l = 0; l < m->ff.rows.size(); ++l) xavier(m->ff.rows[l], m->ff.cols[l]);
+			// a Sine network: CutlassMLP::initialize_params' SIREN branch (cutlass_mlp.cu:1090-1098): the first matrix
+			// U(+-30 / fan_in), every other U(+-sqrt(6 / fan_in)), fan_in the matrix's padded column count (gpu_matrix.h:343-375);
+			// the same draws in the same order
+			auto siren = [&](uint32_t out, uint32_t in, bool first) {
+				const float scale = first ? 30.0f / (float)in : std::sqrt(6.0f / (float)in);
+				for (uint32_t i = 0; i < out * in; ++i) h[off + i] = rnd.next_float() * 2.0f * scale - scale;
+				off += (size_t)out * in;
+			};
+			for (size_t l = 0; l < m->ff.rows.size(); ++l) {
+				if (m->ff.sine()) siren(m->ff.rows[l], m->ff.cols[l], l == 0);
+				else xavier(m->ff.rows[l], m->ff.cols[l]);
+			}
 			float* hg = h.data() + off;
 			const size_t N = h.size() - off, per = 4, n_threads = (N + per - 1) / per, n_pad = (n_threads + 127) / 128 * 128;
 			for (size_t i = 0; i < n_pad; ++i) {
@@ -4307,8 +4331,9 @@ static void module_forward(NeusModule* m, void* stream, uint32_t n, const float*
 		const bool net = m->net();
 		half_t* acts = m->fw.acts.p;
 		if (net && ctx) { ctx->acts.alloc(std::max<size_t>(1, f.acts_halves(n))); acts = ctx->acts.p; }
+		if (net && ctx && f.sine()) ctx->cosz.alloc(std::max<size_t>(1, (size_t)n * f.N * f.W));
 		m->enc.encode(s, n, input, m->enc_params(params), ctx, net ? enc_io(acts, f.in_pad) : enc_io(output, 0));
-		if (net) ff_forward(f, s, n, params, acts, (half_t*)output);
+		if (net) ff_forward(f, s, n, params, acts, (half_t*)output, ctx ? ctx->cosz.p : nullptr);
 	}
 	HIP_CHECK(hipGetLastError());
 }
@@ -4351,13 +4376,13 @@ int neus_module_backward(NeusModule* m, void* stream, const NeusContext* ctx, ui
 			const bool net = m->net();
 			if (net) {
 				if (!params) throw std::runtime_error("module: null params");
-				if (!ctx->acts.p) throw std::runtime_error("module backward: the context is not from this module's forward");
+				if (!ctx->acts.p || (f.sine() && !ctx->cosz.p)) throw std::runtime_error("module backward: the context is not from this module's forward");
 				if (f.out_act != FF_NONE && !output) throw std::runtime_error("FullyFusedMLP backward: the forward output is needed for its output activation");
 			}
 			m->enc.check_backward(ctx, params, dL_dinput, !net);
 			EncIO dy = enc_io(dL_doutput, 0);
 			if (net)
-				dy = enc_io(ff_backward_chain(f, m->fw, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, (const half_t*)output, g != nullptr,
+				dy = enc_io(ff_backward_chain(f, m->fw, s, n, params, ctx->acts.p, ctx->cosz.p, (const half_t*)dL_doutput, (const half_t*)output, g != nullptr,
 				                              m->enc.sink(dL_dinput)), f.in_pad);
 			m->enc.backward(s, n, ctx, input, dy, m->enc_params(params), g && m->enc.n_params() ? g + m->enc_off : nullptr, dL_dinput);
 		}
@@ -4412,13 +4437,13 @@ int neus_module_backward_backward_input(NeusModule* m, void* stream, const NeusC
 					                         "\"second_order\": \"exact\" (the default chain has no forward output for its backward)");
 				if (curved && f.out_act != FF_NONE) ff_output(f, s, n, params, ctx->acts.p, m->fw.y.p);
 				if (m->enc.bbi_reads_dy(ge, dL_dinput))
-					dy.p = const_cast<half_t*>(ff_backward_chain(f, m->fw, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, curved ? m->fw.y.p : nullptr,
+					dy.p = const_cast<half_t*>(ff_backward_chain(f, m->fw, s, n, params, ctx->acts.p, ctx->cosz.p, (const half_t*)dL_doutput, curved ? m->fw.y.p : nullptr,
 					                                             false, FfSink{false, nullptr, 1.f}));
 				Ju = enc_io(g || dL_ddLdoutput || (curved && dL_dinput) ? m->fw.front.p : nullptr, f.in_pad);
 			}
 			m->enc.backward_backward(s, n, ctx, input, dL_ddLdinput, dy, m->enc_params(params), ge, Ju, dL_dinput, curved);
 			if (net && Ju.p) {
-				const half_t* q = ff_bbi_chain(f, m->fw, s, n, params, ctx->acts.p, (const half_t*)dL_doutput, g != nullptr, (half_t*)dL_ddLdoutput,
+				const half_t* q = ff_bbi_chain(f, m->fw, s, n, params, ctx->acts.p, ctx->cosz.p, (const half_t*)dL_doutput, g != nullptr, (half_t*)dL_ddLdoutput,
 				                               ge || dL_dinput, m->enc.sink(dL_dinput));
 				if (q) m->enc.backward_curved(s, n, ctx, input, enc_io(q, f.in_pad), m->enc_params(params), ge, dL_dinput);
 			}

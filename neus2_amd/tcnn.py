@@ -20,7 +20,9 @@ is an empty Parameter.
 
 Networks: "otype" FullyFusedMLP (n_neurons 16, 32, 64 or 128) or CutlassMLP (n_neurons any multiple of 16 from 16 to 512:
 the way to a 256- or 512-wide network, as in tiny-cuda-nn), 1 to 32 hidden layers, up to 128 input and output dims; the
-config is passed through to the native module, which validates it.
+config is passed through to the native module, which validates it. A CutlassMLP also takes "activation": "Sine" (a SIREN,
+initialised as tiny-cuda-nn's: first matrix U(+-30 / fan_in), the others U(+-sqrt(6 / fan_in))), with the exact double
+backward; a FullyFusedMLP refuses it, and no otype takes it as "output_activation".
 
 Two autograd Functions talk to a small backend object (`NativeBackend` over module.Module by default):
     n_params, n_input_dims, n_output_dims (the backend's, possibly padded, output width), param_dtype, output_dtype,
@@ -238,7 +240,7 @@ class Encoding(Module):
 
 class Network(Module):
     """Network(n_input_dims, n_output_dims, network_config, seed=1337): a FullyFusedMLP (width 16 / 32 / 64 / 128) or a
-    CutlassMLP (any multiple of 16 up to 512) on the raw input."""
+    CutlassMLP (any multiple of 16 up to 512; also with "activation": "Sine") on the raw input."""
 
     def __init__(self, n_input_dims, n_output_dims, network_config, seed=1337):
         self.network_config = dict(_text(network_config), gradient_precision="fp32", second_order="exact")
