@@ -297,9 +297,10 @@ uint32_t ff_wgrad_blocks(uint32_t n, bool wide = false);
 void launch_ff_wgrad(hipStream_t s, const FfWgrad& G);
 void launch_ff_input(hipStream_t s, uint32_t n, uint32_t n_in, uint32_t ld, const float* in, float scale, float offset, half_t* x, bool grad);
 void launch_ff_out_delta(hipStream_t s, uint32_t n, uint32_t ld, uint32_t act, const half_t* dL, const half_t* out, half_t* d);
-// encodings.hip: tcnn's parameter-free encodings (identity.h, frequency.h, spherical_harmonics.h, composite.h) as up to 8
-// segments over consecutive input dims, their outputs concatenated; param = n_frequencies / the SH degree
-enum : uint32_t { PF_IDENTITY = 0, PF_FREQUENCY = 1, PF_SH = 2 };
+// encodings.hip: tcnn's parameter-free encodings (identity.h, frequency.h, spherical_harmonics.h, triangle_wave.h, oneblob.h,
+// composite.h) as up to 8 segments over consecutive input dims, their outputs concatenated; param = n_frequencies / the SH
+// degree / n_bins (a power of two <= 128)
+enum : uint32_t { PF_IDENTITY = 0, PF_FREQUENCY = 1, PF_SH = 2, PF_TRIANGLE_WAVE = 3, PF_ONEBLOB = 4 };
 constexpr uint32_t PF_MAX_SEGMENTS = 8;
 struct PfSegment { uint32_t type, in0, dims, out0, param; float scale, offset; };
 struct PfEnc { uint32_t n_seg, n_in, width; PfSegment seg[PF_MAX_SEGMENTS]; };
@@ -309,8 +310,8 @@ struct PfView { void* p; uint64_t ss, sk; uint32_t f32; };
 // columns 1 (features: the bias input of tcnn's padded encodings) or 0 (J u), stored as 16-byte vectors
 void launch_pf_rows(hipStream_t s, const PfEnc& E, uint32_t n, const float* in, const float* u, half_t* rows, uint32_t ld);
 void launch_pf_out(hipStream_t s, const PfEnc& E, uint32_t n, const float* in, const float* u, const PfView& out);
-// u null: dLdx = J^T dLdy; u: the second-order term dLdx_d = u_d sum_k dLdy_k d2y_k/dx_d^2 (0 for Identity and SH
-// segments). One lane per sample, fp32 sums in column order.
+// u null: dLdx = J^T dLdy; u: the second-order term dLdx_d = u_d sum_k dLdy_k d2y_k/dx_d^2 (0 for Identity, SH and
+// TriangleWave segments). One lane per sample, fp32 sums in column order (OneBlob: over its three reachable bins).
 void launch_pf_input_grad(hipStream_t s, const PfEnc& E, uint32_t n, const float* in, const PfView& dLdy, const float* u, float* dLdx);
 // march.hip
 void launch_bitfield_linear(hipStream_t s, const uint8_t* bitfield, uint32_t* lin /* LIN_WORDS */);

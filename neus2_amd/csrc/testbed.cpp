@@ -3507,9 +3507,15 @@ void ff_reduce(const FfNet& f, FfWork& w, hipStream_t s, uint32_t n_blocks, floa
 
 // ---------------------------------------------------------------- the encoding part
 // tcnn's parameter-free encodings from their config (encoding.cu create_encoding; identity.h, frequency.h,
-// spherical_harmonics.h, composite.h): one segment, or a Composite's nested encodings over consecutive input dims (the
-// last may leave n_dims_to_encode out and takes the rest). Host only: every check runs before a device call.
-bool pf_otype(const std::string& ot) { return ot == "Identity" || ot == "Frequency" || ot == "SphericalHarmonics" || ot == "Composite"; }
+// spherical_harmonics.h, triangle_wave.h, oneblob.h, composite.h): one segment, or a Composite's nested encodings over
+// consecutive input dims (the last may leave n_dims_to_encode out and takes the rest); OneBlobFrequency / NRC is the
+// Composite encoding.cu:108-129 expands it into. Host only: every check runs before a device call.
+bool pf_segment_otype(const std::string& ot) {
+	return ot == "Identity" || ot == "Frequency" || ot == "SphericalHarmonics" || ot == "TriangleWave" || ot == "OneBlob";
+}
+bool pf_nrc_otype(const std::string& ot) { return ot == "OneBlobFrequency" || ot == "NRC"; }
+bool pf_otype(const std::string& ot) { return pf_segment_otype(ot) || pf_nrc_otype(ot) || ot == "Composite"; }
+JsonValue json_number(double v) { JsonValue j; j.kind = JsonValue::Number; j.num = v; return j; }
 void pf_add_segment(PfEnc& E, const JsonValue& j, const std::string& ot, uint32_t dims) {
 	if (E.n_seg == PF_MAX_SEGMENTS) throw std::runtime_error("Composite: at most 8 nested encodings");
 	if (dims == 0) throw std::runtime_error(ot + ": at least 1 input dim to encode");
@@ -3526,6 +3532,16 @@ void pf_add_segment(PfEnc& E, const JsonValue& j, const std::string& ot, uint32_
 		const double nf = j.number("n_frequencies", 12);
 		if (nf < 1 || nf > 16) throw std::runtime_error("Frequency: n_frequencies must be in 1..16 on gfx950");
 		g.type = PF_FREQUENCY; g.param = (uint32_t)nf; w = 2 * dims * g.param;
+	} else if (ot == "TriangleWave") {
+		const double nf = j.number("n_frequencies", 12);
+		if (nf < 1 || nf > 16) throw std::runtime_error("TriangleWave: n_frequencies must be in 1..16 on gfx950");
+		g.type = PF_TRIANGLE_WAVE; g.param = (uint32_t)nf; w = dims * g.param;
+	} else if (ot == "OneBlob") {
+		const double nb = j.number("n_bins", 16);
+		if (nb < 1 || nb > 128) throw std::runtime_error("OneBlob: n_bins must be in 1..128 on gfx950");
+		g.param = (uint32_t)nb;
+		if ((double)g.param != nb || (g.param & (g.param - 1)) != 0) throw std::runtime_error("OneBlob: Number of bins must be a power of 2");
+		g.type = PF_ONEBLOB; w = dims * g.param;
 	} else {
 		g.type = PF_IDENTITY; g.scale = (float)j.number("scale", 1.0); g.offset = (float)j.number("offset", 0.0);
 	}
@@ -3536,6 +3552,18 @@ PfEnc pf_from_json(const JsonValue& j, uint32_t n_input_dims) {
 	if (n_input_dims == 0 || n_input_dims > (1u << 16)) throw std::runtime_error("encoding module: n_input_dims must be in 1..65536");
 	PfEnc E{};
 	const std::string ot = j.string("otype", "");
+	if (pf_nrc_otype(ot)) {  // [TriangleWave over 3 dims | OneBlob over 5 | Identity over the rest], none at 8 dims (composite.h:92)
+		if (n_input_dims < 8)
+			throw std::runtime_error(ot + ": n_input_dims must be at least 8 (3 TriangleWave dims and 5 OneBlob dims), but got " + std::to_string(n_input_dims));
+		JsonValue tw, ob, id;
+		tw.kind = ob.kind = id.kind = JsonValue::Object;
+		tw.obj["n_frequencies"] = json_number(j.number("n_frequencies", 12));
+		ob.obj["n_bins"] = json_number(j.number("n_bins", 4));
+		pf_add_segment(E, tw, "TriangleWave", 3);
+		pf_add_segment(E, ob, "OneBlob", 5);
+		if (n_input_dims > 8) pf_add_segment(E, id, "Identity", n_input_dims - 8);
+		return E;
+	}
 	if (ot != "Composite") { pf_add_segment(E, j, ot, n_input_dims); return E; }
 	if (!j.has("nested") || j.at("nested").kind != JsonValue::Array || j.at("nested").arr.empty())
 		throw std::runtime_error("Composite: 'nested' must be a non-empty array of encodings");
@@ -3544,8 +3572,8 @@ PfEnc pf_from_json(const JsonValue& j, uint32_t n_input_dims) {
 		const JsonValue& e = nested[i];
 		if (e.kind != JsonValue::Object) throw std::runtime_error("Composite: 'nested' must be a non-empty array of encodings");
 		const std::string eo = e.string("otype", "");
-		if (eo != "Identity" && eo != "Frequency" && eo != "SphericalHarmonics")
-			throw std::runtime_error("Composite: nested encodings must be Identity, Frequency or SphericalHarmonics");
+		if (!pf_segment_otype(eo))
+			throw std::runtime_error("Composite: nested encodings must be Identity, Frequency or SphericalHarmonics, or TriangleWave or OneBlob");
 		uint32_t dims = 0;
 		if (e.has("n_dims_to_encode")) {
 			const double d = e.number("n_dims_to_encode", 0);
@@ -3566,6 +3594,8 @@ PfEnc pf_from_json(const JsonValue& j, uint32_t n_input_dims) {
 std::string pf_hyper_segment(const PfSegment& g) {
 	if (g.type == PF_SH) return "\"otype\": \"SphericalHarmonics\", \"degree\": " + std::to_string(g.param);
 	if (g.type == PF_FREQUENCY) return "\"otype\": \"Frequency\", \"n_frequencies\": " + std::to_string(g.param);
+	if (g.type == PF_TRIANGLE_WAVE) return "\"otype\": \"TriangleWave\", \"n_frequencies\": " + std::to_string(g.param);
+	if (g.type == PF_ONEBLOB) return "\"otype\": \"OneBlob\", \"n_bins\": " + std::to_string(g.param);
 	return "\"otype\": \"Identity\", \"scale\": " + fmt_float(g.scale) + ", \"offset\": " + fmt_float(g.offset);
 }
 // The grid otypes and what decides between the 3-D 2-feature kernels and the general grid (grid_nd.hip). Host only.
@@ -3930,14 +3960,14 @@ EncSpec enc_from_json(const JsonValue& j, uint32_t n_input_dims, uint32_t batch_
 		return e;
 	}
 	if (pf_otype(ot)) {
-		e.type = EncSpec::Pf; e.pf = pf_from_json(j, n_input_dims); e.composite = ot == "Composite";
+		e.type = EncSpec::Pf; e.pf = pf_from_json(j, n_input_dims); e.composite = !pf_segment_otype(ot);
 		return e;
 	}
 	if (!grid_otype(ot))
-		throw std::runtime_error(with_net ? "network with input encoding: the encoding must be Identity, Frequency, SphericalHarmonics, Composite or "
-		                                    "a grid (HashGrid / Grid / DenseGrid / TiledGrid) on gfx950"
-		                                  : "encoding module: HashGrid / Grid / DenseGrid / TiledGrid, Identity, Frequency, SphericalHarmonics and Composite "
-		                                    "are implemented on gfx950");
+		throw std::runtime_error(with_net ? "network with input encoding: the encoding must be Identity, Frequency, SphericalHarmonics, TriangleWave, "
+		                                    "OneBlob, OneBlobFrequency / NRC, Composite or a grid (HashGrid / Grid / DenseGrid / TiledGrid) on gfx950"
+		                                  : "encoding module: HashGrid / Grid / DenseGrid / TiledGrid, Identity, Frequency, SphericalHarmonics, "
+		                                    "TriangleWave, OneBlob, OneBlobFrequency / NRC and Composite are implemented on gfx950");
 	e.gc = grid_choice(j, n_input_dims);
 	e.type = e.gc.general ? EncSpec::Nd : EncSpec::Hash16;
 	JsonValue none; none.kind = JsonValue::Object;

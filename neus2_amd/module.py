@@ -51,7 +51,7 @@ class Module:
     'encoding' = the HashGrid encoding (input [n, 3] f32; output layout by the config's "output_layout": "AoS" [n, 2L]
     (default: the column-major view cpp::Module gives its caller, cpp_api.cu:58-70), "SoA" [2L, n] (GridEncoding's
     preferred layout, grid.h:2357-2359) or "paired" [L, n, 2] (this build's kernels)), or a parameter-free encoding
-    (Identity, Frequency, SphericalHarmonics, Composite: input [n, n_input_dims] f32, output "AoS" [n, w] or "SoA" [w, n],
+    (Identity, Frequency, SphericalHarmonics, TriangleWave, OneBlob, NRC, Composite: input [n, n_input_dims] f32, output "AoS" [n, w] or "SoA" [w, n],
     unpadded, n_params 0: `params` and `dL_dparams` may be empty tensors or None). A grid that is not the 3-dim, 2-feature,
     hashed, linear one (2 - 4 dims, 1 / 2 / 4 / 8 features, "type" Dense / Tiled, "interpolation" Smoothstep, or "implementation":
     "general") is the general grid: input [n, n_input_dims] f32, output "AoS" [n, F L] or "SoA" [F L, n], any n. dL_dparams is fp16 (tcnn's param
@@ -93,8 +93,9 @@ class Module:
         """tcnn create_network_with_input_encoding (cpp_api.h:108; network_with_input_encoding.h): `encoding` HashGrid (or any
         grid create_encoding accepts, n_input_dims 2 - 4, encoded width F L <= 128, zero-padded to 16),
         Identity ({"scale", "offset"}, identity.h), Frequency ({"n_frequencies": 1..16}), SphericalHarmonics ({"degree": 1..8},
-        3 dims) or Composite ({"nested": [{"n_dims_to_encode", ...}, ...]} of the last three; encoded width <= 128, padded to
-        16 with ones), `network` a FullyFusedMLP of any depth / width (16, 32, 64, 128) / activation, or a CutlassMLP of any width that is
+        3 dims), TriangleWave ({"n_frequencies": 1..16}), OneBlob ({"n_bins": a power of two <= 128}), OneBlobFrequency / NRC
+        ({"n_frequencies", "n_bins"}, >= 8 dims: TriangleWave over 3, OneBlob over 5, Identity over the rest) or Composite
+        ({"nested": [{"n_dims_to_encode", ...}, ...]} of these five segment types; encoded width <= 128, padded to 16 with ones), `network` a FullyFusedMLP of any depth / width (16, 32, 64, 128) / activation, or a CutlassMLP of any width that is
         a multiple of 16 up to 512.
         Params [network matrices in order | grid] (network first, as NetworkWithInputEncoding's set_params_impl,
         network_with_input_encoding.h:262-270); output [n, padded n_output_dims] fp16; the grid's output is zero-padded to
@@ -114,7 +115,8 @@ class Module:
     def create_encoding(cls, encoding, batch_capacity=1 << 18, n_input_dims=3, requested_precision=Precision.Fp16):
         """tcnn create_encoding(n_input_dims, encoding, requested_precision) (cpp_api.h:110; cpp_api.cu:174-180): Fp16 =
         GridEncoding<__half> (fp16 params / output), Fp32 = GridEncoding<float> (f32 params, output and gradients).
-        `encoding` may also be Identity, Frequency, SphericalHarmonics or a Composite of them, on any n_input_dims and any
+        `encoding` may also be Identity, Frequency, SphericalHarmonics, TriangleWave, OneBlob, OneBlobFrequency / NRC or a
+        Composite of the first five, on any n_input_dims (NRC: at least 8) and any
         n >= 1: no parameters, output and dL_doutput in the requested precision, "output_layout" AoS or SoA.
         Grids: otype HashGrid / Grid ("type": "Hash" | "Dense" | "Tiled") or DenseGrid / TiledGrid, n_input_dims 2 - 4,
         n_features_per_level 1 / 2 / 4 / 8, "interpolation": "Linear" | "Smoothstep"; "implementation": "general" puts the 3-dim,

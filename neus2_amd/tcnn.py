@@ -15,8 +15,10 @@ the parameters) is not supported.
 
 Encodings: grids (HashGrid / Grid / DenseGrid / TiledGrid: 2, 3 or 4 input dims, 1, 2, 4 or 8 features per level, "type" Hash /
 Dense / Tiled, "interpolation" Linear / Smoothstep; with Smoothstep the double backward carries the grid's diagonal second
-derivatives), and the parameter-free Identity, Frequency, SphericalHarmonics and Composite (of those three), whose `params`
-is an empty Parameter.
+derivatives), and the parameter-free Identity, Frequency, SphericalHarmonics, TriangleWave (1-16 frequencies), OneBlob
+(n_bins a power of two up to 128), OneBlobFrequency / NRC (TriangleWave over 3 dims, OneBlob over 5, Identity over the rest;
+at least 8 dims) and Composite (of the five segment types), whose `params` is an empty Parameter. OneBlob's second
+derivative is continuous and TriangleWave's is zero: both support the double backward.
 
 Networks: "otype" FullyFusedMLP (n_neurons 16, 32, 64 or 128) or CutlassMLP (n_neurons any multiple of 16 from 16 to 512:
 the way to a 256- or 512-wide network, as in tiny-cuda-nn), 1 to 32 hidden layers, up to 128 input and output dims; the
@@ -220,7 +222,7 @@ def _text(cfg):
 
 class Encoding(Module):
     """Encoding(n_input_dims, encoding_config, seed=1337, dtype=None): a grid (2 - 4 input dims), or a parameter-free Identity /
-    Frequency / SphericalHarmonics / Composite encoding (`params` is then empty). dtype None / torch.float16: fp16 table
+    Frequency / SphericalHarmonics / TriangleWave / OneBlob / NRC / Composite encoding (`params` is then empty). dtype None / torch.float16: fp16 table
     and output (loss_scale 128); torch.float32: the fp32 encoding (loss_scale 1)."""
 
     def __init__(self, n_input_dims, encoding_config, seed=1337, dtype=None):
@@ -256,7 +258,7 @@ class Network(Module):
 
 class NetworkWithInputEncoding(Module):
     """NetworkWithInputEncoding(n_input_dims, n_output_dims, encoding_config, network_config, seed=1337): a grid (2 - 4 dims),
-    Identity, Frequency, SphericalHarmonics or Composite encoding in front of a FullyFusedMLP, as one module with
+    Identity, Frequency, SphericalHarmonics, TriangleWave, OneBlob, NRC or Composite encoding in front of a FullyFusedMLP, as one module with
     parameters [network | grid] (the network alone for the parameter-free encodings)."""
 
     def __init__(self, n_input_dims, n_output_dims, encoding_config, network_config, seed=1337):

@@ -6,6 +6,9 @@ halves with no arithmetic) at n = 2^18:
     sh4         SphericalHarmonics(4)                                      3 dims -> in_pad 16
     freq6       Frequency(3, F = 6)                                        3 dims -> in_pad 48
     composite   [Identity(6) | SphericalHarmonics(4)]                      9 dims -> in_pad 32 (22 columns + 10 ones)
+    tri12       TriangleWave(3, F = 12)                                    3 dims -> in_pad 48 (36 columns + 12 ones)
+    oneblob64   OneBlob(2, n_bins = 64)                                    2 dims -> in_pad 128
+    nrc         NRC: [TriangleWave(3, 12) | OneBlob(5, 4) | Identity(1)]   9 dims -> in_pad 64 (57 columns + 7 ones)
 
 Both launchers are C++ functions of libneus2_hip.so (not part of the C ABI); they are found by name in the library's
 dynamic symbol table and called through ctypes with their by-reference arguments as pointers. A kernel of a few
@@ -18,7 +21,7 @@ over the median, and that rate over the HBM peak of 8 TB/s. At these sizes (4 - 
 Cache, so the share is of a bound the kernel is not actually held to: read it as a common scale for the two kernels.
 One process; the whole run stops at --time-limit seconds. One JSON line per case, the last line a summary.
 
-    python scripts/bench_encodings.py [--log profiles/encodings_bench.log]
+    python scripts/bench_encodings.py [--cases sh4,freq6,composite] [--log profiles/encodings_bench.log]
 """
 import argparse
 import ctypes as C
@@ -32,7 +35,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 HBM_PEAK = 8.0e12
 
-PF_IDENTITY, PF_FREQUENCY, PF_SH = 0, 1, 2
+PF_IDENTITY, PF_FREQUENCY, PF_SH, PF_TRIANGLE_WAVE, PF_ONEBLOB = 0, 1, 2, 3, 4
 
 
 class PfSegment(C.Structure):
@@ -48,7 +51,7 @@ def descriptor(segments):
     """segments: (type, dims, param, scale, offset) in order"""
     E = PfEnc()
     for i, (ty, dims, param, scale, offset) in enumerate(segments):
-        w = param * param if ty == PF_SH else (2 * dims * param if ty == PF_FREQUENCY else dims)
+        w = {PF_SH: param * param, PF_FREQUENCY: 2 * dims * param, PF_TRIANGLE_WAVE: dims * param, PF_ONEBLOB: dims * param}.get(ty, dims)
         E.seg[i] = PfSegment(ty, E.n_in, dims, E.width, param, scale, offset)
         E.n_in += dims
         E.width += w
@@ -60,6 +63,9 @@ CASES = {
     "sh4": [(PF_SH, 3, 4, 1.0, 0.0)],
     "freq6": [(PF_FREQUENCY, 3, 6, 1.0, 0.0)],
     "composite": [(PF_IDENTITY, 6, 0, 1.0, 0.0), (PF_SH, 3, 4, 1.0, 0.0)],
+    "tri12": [(PF_TRIANGLE_WAVE, 3, 12, 1.0, 0.0)],
+    "oneblob64": [(PF_ONEBLOB, 2, 64, 1.0, 0.0)],
+    "nrc": [(PF_TRIANGLE_WAVE, 3, 12, 1.0, 0.0), (PF_ONEBLOB, 5, 4, 1.0, 0.0), (PF_IDENTITY, 1, 0, 1.0, 0.0)],
 }
 
 
@@ -78,6 +84,7 @@ def main():
     ap.add_argument("--windows", type=int, default=21, help="timed windows per kernel")
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--time-limit", type=int, default=240)
+    ap.add_argument("--cases", default=",".join(CASES), help="comma-separated case names")
     ap.add_argument("--log", default=None)
     a = ap.parse_args()
     signal.alarm(a.time_limit)  # the default action ends the process
@@ -95,8 +102,8 @@ def main():
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     n = a.n
     lines = []
-    for name, segs in CASES.items():
-        E = descriptor(segs)
+    for name in a.cases.split(","):
+        E = descriptor(CASES[name])
         D, in_pad = E.n_in, (E.width + 15) // 16 * 16
         x = torch.from_numpy(np.random.default_rng(0).uniform(0, 1, (n, D)).astype(np.float32)).cuda()
         rows = torch.zeros((n, in_pad), dtype=torch.float16, device="cuda")
