@@ -5,6 +5,7 @@
 //   k_gnd_forward : kernel_grid (grid.h:174-369)
 //   k_gnd_backward: kernel_grid_backward (grid.h:371-500): one fp32 atomicAdd per corner and feature. As in grid_f32.hip
 //                   the order of the float atomics varies from call to call, so dL_dparams is NOT bitwise repeatable
+//                   ("gradient_scatter": "binned" takes grid_nd_scatter.hip instead, here and for k_gnd_bbi's dL_dparams)
 //   k_gnd_dx      : kernel_grid_backward_input (grid.h:804-830), the Jacobian gathered again from the input: per (level,
 //                   sample) terms into a scratch [D l + d][n], added in level order by k_gnd_sum (bitwise repeatable)
 //   k_gnd_bbi     : backward_backward_input (grid.h:880-1181): the second-order dL_dparams (atomics), dL_ddLdoutput = J u
@@ -16,7 +17,7 @@
 // Tensors of the caller (output, dL_doutput, dL_ddLdoutput) go through a PfView (pointer, sample stride, column stride,
 // precision), so the same kernels serve the stand-alone AoS / SoA tensors and a FullyFusedMLP's fp16 rows [n][in_pad]
 // (`pad` zero columns after the F L features).
-#include "kernels.h"
+#include "grid_nd_common.h"
 #include <algorithm>
 #include <cmath>
 #include <stdexcept>
@@ -26,95 +27,12 @@ namespace neus {
 
 namespace {
 
-template <int D> struct NdPos {
-	uint32_t g[D];
-	float w[D], dw[D], ddw[D];  // interpolation weight of the upper corner along d, its first and second derivative in the fraction
-	float scale;
-	uint32_t hsize, res;
-	bool hash, pow2;
-};
-
-// pos_fract (common_device.h:404-434): fmaf(x, scale, 0.5f), floor and fraction as level_setup (grid_common.h); Smoothstep
-// t^2 (3 - 2 t), derivative 6 t (1 - t), second derivative 6 - 12 t
-template <int D> __device__ __forceinline__ NdPos<D> nd_setup(const GridNd& G, uint32_t l, const float* __restrict__ x) {
-	NdPos<D> s;
-	s.scale = G.gl.scale[l]; s.res = G.gl.res[l]; s.hsize = G.gl.offset[l + 1] - G.gl.offset[l];
-	s.hash = G.type == GRID_ND_HASH;
-	s.pow2 = (s.hsize & (s.hsize - 1)) == 0;
-#pragma unroll
-	for (int d = 0; d < D; ++d) {
-		const float p = __builtin_fmaf(x[d], s.scale, 0.5f);
-		const float fl = floorf(p);
-		s.g[d] = (uint32_t)(int)fl;
-		const float t = p - fl;
-		if (G.smooth) {
-			s.w[d] = t * t * (3.f - 2.f * t);
-			s.dw[d] = 6.f * t * (1.f - t);
-			s.ddw[d] = 6.f - 12.f * t;
-		} else {
-			s.w[d] = t; s.dw[d] = 1.f; s.ddw[d] = 0.f;
-		}
-	}
-	return s;
-}
-
-// grid_index (grid.h:137-153): strides accumulate while stride <= level size (the early exit makes a Tiled level tile), a
-// Hash level smaller than its resolution takes the xor of pos[d] * prime[d]; modulo the level size
-template <int D> __device__ __forceinline__ uint32_t nd_index(const NdPos<D>& s, uint32_t c) {
-	constexpr uint32_t primes[4] = {1u, 2654435761u, 805459861u, 3674653429u};
-	uint32_t stride = 1, index = 0, h = 0;
-#pragma unroll
-	for (int d = 0; d < D; ++d) {
-		const uint32_t p = s.g[d] + ((c >> d) & 1u);
-		if (stride <= s.hsize) { index += p * stride; stride *= s.res; }
-		h ^= p * primes[d];
-	}
-	if (s.hash && s.hsize < stride) index = h;
-	return s.pow2 ? index & (s.hsize - 1) : index % s.hsize;
-}
-
-template <int D> __device__ __forceinline__ float nd_side(const NdPos<D>& s, uint32_t c, int d) { return (c & (1u << d)) ? s.w[d] : 1.f - s.w[d]; }
-// the corner's interpolation weight
-template <int D> __device__ __forceinline__ float nd_weight(const NdPos<D>& s, uint32_t c) {
-	float w = 1.f;
-#pragma unroll
-	for (int d = 0; d < D; ++d) w *= nd_side(s, c, d);
-	return w;
-}
-// sigma_cj prod_{d != j} side_d: the corner's weight differentiated in the weight of axis j (sigma = +-1 by corner bit j)
-template <int D> __device__ __forceinline__ float nd_dweight(const NdPos<D>& s, uint32_t c, int j) {
-	float w = (c & (1u << j)) ? 1.f : -1.f;
-#pragma unroll
-	for (int d = 0; d < D; ++d) if (d != j) w *= nd_side(s, c, d);
-	return w;
-}
-// sigma_ci sigma_cj prod_{d != i, j} side_d
-template <int D> __device__ __forceinline__ float nd_ddweight(const NdPos<D>& s, uint32_t c, int i, int j) {
-	float w = (((c >> i) ^ (c >> j)) & 1u) ? -1.f : 1.f;
-#pragma unroll
-	for (int d = 0; d < D; ++d) if (d != i && d != j) w *= nd_side(s, c, d);
-	return w;
-}
-
 // the F features of one table row as one vector load
 template <int F, class T> struct alignas(F * sizeof(T) > 16 ? 16 : F * sizeof(T)) NdRow { T v[F]; };
 template <int F, class T> __device__ __forceinline__ void nd_load(const T* __restrict__ p, float v[F]) {
 	const NdRow<F, T> r = *(const NdRow<F, T>*)p;
 #pragma unroll
 	for (int f = 0; f < F; ++f) v[f] = (float)r.v[f];
-}
-
-__device__ __forceinline__ float view_load(const PfView& v, uint32_t i, uint32_t k) {
-	const size_t a = (size_t)i * v.ss + (size_t)k * v.sk;
-	return v.f32 ? ((const float*)v.p)[a] : (float)((const half_t*)v.p)[a];
-}
-__device__ __forceinline__ void view_store(const PfView& v, uint32_t i, uint32_t k, float x) {
-	const size_t a = (size_t)i * v.ss + (size_t)k * v.sk;
-	if (v.f32) ((float*)v.p)[a] = x; else ((half_t*)v.p)[a] = (half_t)x;
-}
-template <int D> __device__ __forceinline__ void nd_coords(const float* __restrict__ coords, uint32_t i, float x[D]) {
-#pragma unroll
-	for (int d = 0; d < D; ++d) x[d] = coords[(size_t)i * D + d];
 }
 
 template <int D, int F, class T>

@@ -524,6 +524,16 @@ void launch_grid_nd_input_grad(hipStream_t s, uint32_t n, const GridNd& G, uint3
 // (ddLdy.p null: skipped), dLdx [n][D] overwritten (null: skipped; needs partial)
 void launch_grid_nd_bbi(hipStream_t s, uint32_t n, const GridNd& G, uint32_t valid_level, const float* coords, const void* table, bool table_f32,
                         const float* ddx, const PfView& dLdy, float* grads, const PfView& ddLdy, uint32_t pad, float* partial, float* dLdx);
+// "gradient_scatter": "binned" (grid_nd_scatter.hip): the parameter gradient as int64 fixed-point sums of resolution 2^-32,
+// converted to fp32 once: bitwise independent of the order of the samples. ddx null: the first-order gradient (weights
+// w_c), else the second-order one (weights a_c of backward_backward_input). grads: every parameter is written (add: one
+// fp32 add onto what is there; the levels above the valid one then stay). acc / poison: grid_nd_scatter_values(G) int64
+// accumulators and as many bytes, zero on entry and zero again when the launches have run; levels whose accumulators
+// exceed ND_SCATTER_CAP_BYTES together go through them in consecutive groups.
+constexpr uint64_t ND_SCATTER_CAP_BYTES = 1ull << 30;
+uint64_t grid_nd_scatter_values(const GridNd& G);
+void launch_grid_nd_scatter(hipStream_t s, uint32_t n, const GridNd& G, uint32_t valid_level, const float* coords, const float* ddx, const PfView& dLdy,
+                            float* grads, bool add, long long* acc, uint8_t* poison);
 // paired [L][n] <-> sample rows [n][ld] (features in columns [0, 2L), zero padding up to ld): a FullyFusedMLP's input
 void launch_enc_to_rows(hipStream_t s, uint32_t n, uint32_t L, const uint32_t* paired, half_t* rows, uint32_t ld);
 void launch_enc_from_rows(hipStream_t s, uint32_t n, uint32_t L, const half_t* rows, uint32_t ld, uint32_t* paired);

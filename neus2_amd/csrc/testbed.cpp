@@ -3600,7 +3600,9 @@ std::string pf_hyper_segment(const PfSegment& g) {
 }
 // The grid otypes and what decides between the 3-D 2-feature kernels and the general grid (grid_nd.hip). Host only.
 bool grid_otype(const std::string& ot) { return ot == "HashGrid" || ot == "Grid" || ot == "DenseGrid" || ot == "TiledGrid"; }
-struct GridChoice { bool general; uint32_t type; bool smooth; };
+// scatter: "gradient_scatter" (this build's key): 0 = not set, 1 = "atomic" (what not set means), 2 = "binned": dL_dparams of the
+// general grid as order-independent int64 fixed-point sums (grid_nd_scatter.hip); the fp16 3-D 2-feature kernels are binned as they are
+struct GridChoice { bool general; uint32_t type; bool smooth; uint32_t scatter; };
 GridChoice grid_choice(const JsonValue& j, uint32_t n_input_dims) {
 	const std::string ot = j.string("otype", "HashGrid");
 	const std::string ty = j.string("type", ot == "DenseGrid" ? "Dense" : (ot == "TiledGrid" ? "Tiled" : "Hash"));
@@ -3621,6 +3623,11 @@ GridChoice grid_choice(const JsonValue& j, uint32_t n_input_dims) {
 	const double nf = j.number("n_features_per_level", 2);
 	if (nf != 1 && nf != 2 && nf != 4 && nf != 8) throw std::runtime_error("grid encoding: n_features_per_level must be 1, 2, 4 or 8");
 	c.general = im == "general" || n_input_dims != 3 || nf != 2 || c.type != GRID_ND_HASH || c.smooth;
+	if (j.has("gradient_scatter")) {
+		const std::string gs = j.string("gradient_scatter", "");
+		if (gs != "atomic" && gs != "binned") throw std::runtime_error("grid encoding: gradient_scatter must be atomic or binned, but got '" + gs + "'");
+		c.scatter = gs == "binned" ? 2 : 1;
+	}
 	return c;
 }
 
@@ -3663,9 +3670,16 @@ struct Enc : EncSpec {
 	Dev<half_t> zero_h;
 	Dev<float> partial;               // the grids: dL_dinput's per-level terms [n_in L][capacity] (first use)
 	Dev<float> dx_tmp;                // in front of a network with act'' terms: the forward-path part of dL_dinput [capacity][n_in] (first use)
+	Dev<long long> sc_acc;            // Nd, "gradient_scatter": "binned": int64 accumulators and poison bytes, zero between calls (first use)
+	Dev<uint8_t> sc_poison;
 
 	// ---- description
 	bool keeps_dydx() const { return type == Hash16 || type == Hash32; }
+	bool binned() const { return type == Nd && gc.scatter == 2; }
+	// "gradient_scatter" is echoed only when the config set it
+	std::string hyper_scatter() const {
+		return gc.scatter ? std::string(", \"gradient_scatter\": \"") + (gc.scatter == 2 ? "binned" : "atomic") + "\"" : "";
+	}
 	uint32_t L() const { return core->lay.L; }
 	uint32_t valid() const { return core->valid_level_at(training_step); }
 	uint64_t n_params() const {
@@ -3694,14 +3708,14 @@ struct Enc : EncSpec {
 			       std::to_string(c.log2_hashmap_size) + ", \"base_resolution\": " + std::to_string(c.base_resolution) + ", \"per_level_scale\": " +
 			       fmt_float(c.per_level_scale) + ", \"interpolation\": \"" + (nd.smooth ? "Smoothstep" : "Linear") + "\", \"valid_level_scale\": " +
 			       fmt_float(c.valid_level_scale) + ", \"base_valid_level_scale\": " + fmt_float(c.base_valid_level_scale) + ", \"base_training_step\": " +
-			       std::to_string(c.base_training_step);
+			       std::to_string(c.base_training_step) + hyper_scatter();
 		}
 		default: {  // in front of a network the progressive-level settings are not echoed
 			const std::string s = "\"otype\": \"HashGrid\", \"n_levels\": " + std::to_string(c.n_levels) + ", \"n_features_per_level\": 2, \"log2_hashmap_size\": " +
 			                      std::to_string(c.log2_hashmap_size) + ", \"base_resolution\": " + std::to_string(c.base_resolution) +
 			                      ", \"per_level_scale\": " + fmt_float(c.per_level_scale);
-			if (!standalone) return s;
-			return s + ", \"valid_level_scale\": " + fmt_float(c.valid_level_scale) + ", \"base_valid_level_scale\": " + fmt_float(c.base_valid_level_scale) +
+			if (!standalone) return s + hyper_scatter();
+			return s + hyper_scatter() + ", \"valid_level_scale\": " + fmt_float(c.valid_level_scale) + ", \"base_valid_level_scale\": " + fmt_float(c.base_valid_level_scale) +
 			       ", \"base_training_step\": " + std::to_string(c.base_training_step);
 		}
 		}
@@ -3733,6 +3747,16 @@ struct Enc : EncSpec {
 		}
 	}
 	float* scratch() { partial.alloc((size_t)n_in * L() * capacity); return partial.p; }
+	// the binned scatter of the general grid: w_c dy (u null) or a_c dy into g, every parameter written; `add`: added onto g
+	void nd_scatter(hipStream_t s, uint32_t n, const float* input, const float* u, EncIO dy, float* g, bool add) {
+		if (!sc_acc.p) {
+			const uint64_t values = grid_nd_scatter_values(nd);
+			sc_acc.alloc(values); sc_poison.alloc(values);
+			HIP_CHECK(hipMemsetAsync(sc_acc.p, 0, values * sizeof(long long), s));
+			HIP_CHECK(hipMemsetAsync(sc_poison.p, 0, values, s));
+		}
+		launch_grid_nd_scatter(s, n, nd, valid(), input, u, view(dy, n), g, add, sc_acc.p, sc_poison.p);
+	}
 	// backward_backward_input's dL_dinput needs the encoding's second derivative: none is implemented for the spherical
 	// harmonics (nor has tcnn's SphericalHarmonicsEncoding a backward_backward_input)
 	void check_bbi_sh(const float* dL_dinput) const {
@@ -3859,7 +3883,9 @@ struct Enc : EncSpec {
 			launch_grid_f32_backward(s, n, core->gl, valid(), input, (const float*)dy.p, layout, g, ctx->dydx.p, dL_dinput);
 			break;
 		case Nd:  // kernel_grid_backward by fp32 atomics into a zeroed buffer; dL_dinput with the Jacobian gathered again from the input
-			if (g) {
+			if (g && binned()) {
+				nd_scatter(s, n, input, nullptr, dy, g, false);
+			} else if (g) {
 				HIP_CHECK(hipMemsetAsync(g, 0, (size_t)n_params() * 4, s));
 				launch_grid_nd_backward(s, n, nd, valid(), input, view(dy, n), g);
 			}
@@ -3917,9 +3943,10 @@ struct Enc : EncSpec {
 			if (dL_dinput) launch_grid_f32_ddx(s, n, core->gl, valid(), input, (const float*)params, (const float*)dy.p, layout, u, scratch(), dL_dinput);
 			break;
 		case Nd:  // one launch: atomics into a zeroed buffer, J u, and dL_dinput (mixed terms, and the diagonal ones with Smoothstep)
-			if (g) HIP_CHECK(hipMemsetAsync(g, 0, (size_t)n_params() * 4, s));
-			launch_grid_nd_bbi(s, n, nd, valid(), input, params, !Ju.ld && f32, u, view(dy, n), g, view(Ju, n), pad(Ju), dL_dinput ? scratch() : nullptr,
-			                   dL_dinput);
+			if (g && binned()) nd_scatter(s, n, input, u, dy, g, false);  // the scatter on its own; the launch below without it
+			else if (g) HIP_CHECK(hipMemsetAsync(g, 0, (size_t)n_params() * 4, s));
+			launch_grid_nd_bbi(s, n, nd, valid(), input, params, !Ju.ld && f32, u, view(dy, n), binned() ? nullptr : g, view(Ju, n), pad(Ju),
+			                   dL_dinput ? scratch() : nullptr, dL_dinput);
 			break;
 		}
 	}
@@ -3939,8 +3966,9 @@ struct Enc : EncSpec {
 			if (dx) launch_enc_input_grad(s, n, n, L(), (const half_t*)enc_tmp.p, ctx->dydx.p, dx, 3);
 			break;
 		}
-		case Nd:  // atomics on top of backward_backward's: its memset stands for both
-			if (g) launch_grid_nd_backward(s, n, nd, valid(), input, view(q, n), g);
+		case Nd:  // atomics on top of backward_backward's: its memset stands for both (binned: its sums added onto backward_backward's, one fp32 add each)
+			if (g && binned()) nd_scatter(s, n, input, nullptr, q, g, true);
+			else if (g) launch_grid_nd_backward(s, n, nd, valid(), input, view(q, n), g);
 			if (dx) launch_grid_nd_input_grad(s, n, nd, valid(), input, params, false, view(q, n), scratch(), dx);
 			break;
 		default: break;  // Identity: the network's layer 0 wrote dL_dinput (FfSink)
@@ -4141,6 +4169,9 @@ int neus_module_create_encoding(uint32_t n_input_dims, const char* encoding_json
 			if (e.type == EncSpec::Nd) throw std::runtime_error("general grid encoding: output_layout AoS or SoA (paired is the 3-D, 2-feature fp16 kernels' layout)");
 			if (f32) throw std::runtime_error("fp32 HashGrid: output_layout AoS or SoA (paired is the fp16 kernels' layout)");
 		}
+		if (f32 && e.type == EncSpec::Hash16 && e.gc.scatter == 2)
+			throw std::runtime_error("fp32 HashGrid: gradient_scatter binned is not implemented on the 3-D 2-feature fp32 kernels; "
+			                         "\"implementation\": \"general\" runs this config on the general grid, which has it");
 		if (f32 && e.type == EncSpec::Hash16) e.type = EncSpec::Hash32;
 		auto m = new_module(e, FfNet{}, j, batch_capacity);
 		m->enc.f32 = f32;

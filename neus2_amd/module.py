@@ -65,6 +65,9 @@ class Module:
         hp = self.hyperparams()
         self.output_layout = hp.get("output_layout", "AoS")
         self.gradient_precision = hp.get("gradient_precision", "fp16")
+        # a grid's "gradient_scatter" ("binned": order-independent parameter gradients), "atomic" when the config leaves it out
+        enc = hp.get("encoding")
+        self.gradient_scatter = (enc if isinstance(enc, dict) else hp).get("gradient_scatter", "atomic")
         self.precision = hp.get("precision", "fp16")
 
     @classmethod

@@ -15,7 +15,8 @@ the parameters) is not supported.
 
 Encodings: grids (HashGrid / Grid / DenseGrid / TiledGrid: 2, 3 or 4 input dims, 1, 2, 4 or 8 features per level, "type" Hash /
 Dense / Tiled, "interpolation" Linear / Smoothstep; with Smoothstep the double backward carries the grid's diagonal second
-derivatives), and the parameter-free Identity, Frequency, SphericalHarmonics, TriangleWave (1-16 frequencies), OneBlob
+derivatives; "gradient_scatter": "binned" in a grid's config makes its `params.grad` bitwise repeatable: int64 fixed-point sums
+in place of float atomics), and the parameter-free Identity, Frequency, SphericalHarmonics, TriangleWave (1-16 frequencies), OneBlob
 (n_bins a power of two up to 128), OneBlobFrequency / NRC (TriangleWave over 3 dims, OneBlob over 5, Identity over the rest;
 at least 8 dims) and Composite (of the five segment types), whose `params` is an empty Parameter. OneBlob's second
 derivative is continuous and TriangleWave's is zero: both support the double backward.
