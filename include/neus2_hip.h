@@ -369,6 +369,10 @@ int neus_debug_set_lds_fill_all(NeusTestbed* tb, uint32_t pattern);
 /* Test hook: every training step launches a no-op kernel of n_blocks workgroups before each of its kernels, shifting the
  * round-robin workgroup -> XCD placement (0: off); the step's results must not depend on the placement. */
 int neus_debug_set_xcd_shift(NeusTestbed* tb, uint32_t n_blocks);
+/* Test hook, process-wide: nonzero keeps the hash-grid encode and the region scatter's binning on their generic kernels
+ * (grid_index with its runtime modulo, one run sum per corner, 64-bit offsets) instead of the direct forms chosen for
+ * dense / power-of-two level tables; the two must agree bitwise (0: off, the default). */
+int neus_debug_set_grid_generic(uint32_t on);
 /* Development: the last step's compacted training batch (coords batch x 7 f32, dL/doutput batch x 16 fp16 bits) and
  * per-ray losses (2^18 f32); host buffers, each nullable. */
 int neus_debug_get_batch(NeusTestbed* tb, float* coords_out, uint16_t* dl_dout_out, float* loss_out);

@@ -25,6 +25,14 @@ __device__ __forceinline__ uint32_t load_n(const uint32_t* n_ptr, uint32_t n_fix
 // reference's fill_rollover_and_rescale copies (my_tcnn common_device.h:515-535): every level reads record i % n_in,
 // and the level-0 blocks write the copies (coordinates, and dL/doutput scaled by n_in / n_elements) for the kernels
 // after this one (k_rollover's work, without its launch).
+//
+// DIRECT (the host's choice, encode_direct_ok): the sample loop of a level holds only that level's work. Corner entries
+// come from corner_entries (no division); the table, enc and the six dy/dx rows are addressed by 32-bit byte offsets
+// from the level's wave-uniform bases; a level above valid_level only stores its zeros; and the rollover copies are a
+// loop of their own after the sample loop of the level-0 blocks, over the records past n_in alone. Same values, same
+// writers. The generic form below is the fall-back for shapes past the 32-bit offsets or level tables that
+// corner_entries does not cover.
+template <bool DIRECT>
 __global__ void __launch_bounds__(256) k_grid_encode(
 	const uint32_t* __restrict__ n_ptr, uint32_t n_fixed, uint32_t ld,
 	const float* __restrict__ coords, uint32_t coord_stride,
@@ -34,6 +42,57 @@ __global__ void __launch_bounds__(256) k_grid_encode(
 	const uint32_t l = blockIdx.y;
 	const half_t* gp = grid + (size_t)gl.offset[l] * 2;
 	const uint32_t n_in = ro.n_in_ptr ? min(*ro.n_in_ptr, ro.n_elements) : 0xffffffffu;
+	if constexpr (DIRECT) {
+		const uint32_t i0 = blockIdx.x * blockDim.x + threadIdx.x, istep = gridDim.x * blockDim.x;
+		char* encl = (char*)(enc + (size_t)l * ld);
+		char* dyl = dydx ? (char*)(dydx + (size_t)6 * l * ld) : nullptr;
+		if (l > valid_level) {
+			for (uint32_t i = i0; i < n; i += istep) {
+				*(uint32_t*)(encl + (i << 2)) = 0u;
+				if (dydx) {
+#pragma unroll
+					for (uint32_t k = 0; k < 6; ++k) *(float*)(dyl + ((k * ld + i) << 2)) = 0.0f;
+				}
+			}
+		} else {
+			const char* tab = (const char*)gp;
+			const float scale = gl.scale[l];
+			const uint32_t res = gl.res[l], hsize = gl.offset[l + 1] - gl.offset[l];
+			const bool dense = (gl.dense_bits >> l) & 1u;
+			for (uint32_t i = i0; i < n; i += istep) {
+				const uint32_t src = i < n_in ? i : i % n_in;  // (n_in > 0 whenever n > 0: n_train is 0 without records)
+				const float* c = (const float*)((const char*)coords + ((src * coord_stride) << 2));
+				const LevelSetup s = level_setup(scale, res, hsize, c[0], c[1], c[2]);
+				uint32_t e[8];
+				corner_entries(s, dense, e);
+				h2 v[8];
+#pragma unroll
+				for (int k = 0; k < 8; ++k) v[k] = *(const h2*)(tab + (e[k] << 2));
+				const h2 out = interp_features(s, v);
+				*(uint32_t*)(encl + (i << 2)) = *(const uint32_t*)&out;
+				if (dydx) {
+					float gr[2][3];
+					interp_dydx(s, v, gr);
+#pragma unroll
+					for (uint32_t k = 0; k < 6; ++k) *(float*)(dyl + ((k * ld + i) << 2)) = gr[k / 3][k % 3];
+				}
+			}
+		}
+		if (l == 0 && n_in < n) {
+			// rows i >= n_in are written, rows i % n_in < n_in read (by every level's sample loop too): the const input
+			// view and ro.coords never meet on an element
+			for (uint32_t i = n_in + i0; i < n; i += istep) {
+				const uint32_t src = i % n_in;
+				for (uint32_t k = 0; k < coord_stride; ++k) ro.coords[(size_t)i * coord_stride + k] = coords[(size_t)src * coord_stride + k];
+#pragma unroll
+				for (int k = 0; k < OUT_W; ++k) {
+					const float r = (float)ro.dL_dout[(size_t)src * OUT_W + k];
+					ro.dL_dout[(size_t)i * OUT_W + k] = (half_t)(r * n_in / ro.n_elements);
+				}
+			}
+		}
+		return;
+	}
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
 		const uint32_t src = i < n_in ? i : i % n_in;  // (n_in > 0 whenever n > 0: n_train is 0 without records)
 		if (l == 0 && i != src) {
@@ -194,6 +253,29 @@ __device__ __forceinline__ void corner_contribution(const ScatterLevel& L, uint3
 	a1 = L.dl1 * wc + L.g1 * w2;
 	const uint32_t gx = L.s.g[0] + (idx & 1), gy = L.s.g[1] + ((idx >> 1) & 1), gz = L.s.g[2] + ((idx >> 2) & 1);
 	gidx = L.off + grid_index(L.s.hsize, L.s.res, gx, gy, gz);
+}
+// a0 / a1 of corner_contribution with its roundings written out, for a caller that evaluates the 8 corners in one
+// basic block (corner_run_sums). In the per-corner loops above the compiler contracts a multiply into the add it feeds
+// only where both sit in one corner's block: the last product of the y term and of the z term is fused into w2 on the
+// corner that computes it first (bit gd clear: the subtracted one) and arrives rounded, from that corner's block, on
+// its partner (bit gd set); the x term likewise (added to zero: the same value either way); dl * wc is fused into the
+// sum with the rounded g * w2. With the 8 corners in one block every product could be fused, which moves a record by an
+// fp32 ulp - and its fp16 rounding now and then. Which products the per-corner loops fuse is the compiler's choice: a
+// compiler upgrade can change it and break the bitwise equality of this form with the binned and wide paths;
+// tests/test_gpu_scatter_runs.py compares the two forms bitwise and fails then. (Stating the roundings once in
+// corner_contribution, under contract(off), for every path would end the dependence.)
+__device__ __forceinline__ void corner_values(const ScatterLevel& L, uint32_t idx, float& a0, float& a1) {
+#pragma clang fp contract(off)
+	float f[3];
+#pragma unroll
+	for (int d = 0; d < 3; ++d) f[d] = (idx & (1u << d)) ? L.s.pos[d] : 1.f - L.s.pos[d];
+	const float wc = f[0] * f[1] * f[2];
+	const float u0 = L.vin[0] * f[1], u1 = L.vin[1] * f[0], u2 = L.vin[2] * f[0];
+	float w2 = (idx & 1u) ? 0.f + u0 * f[2] : __builtin_fmaf(-f[2], u0, 0.f);
+	w2 = (idx & 2u) ? w2 + u1 * f[2] : __builtin_fmaf(-f[2], u1, w2);
+	w2 = (idx & 4u) ? w2 + u2 * f[1] : __builtin_fmaf(-f[1], u2, w2);
+	a0 = __builtin_fmaf(L.dl0, wc, L.g0 * w2);
+	a1 = __builtin_fmaf(L.dl1, wc, L.g1 * w2);
 }
 __device__ __forceinline__ ScatterLevel scatter_level_ab(const GridLevels& gl, uint32_t l, float x, float y, float z, uint32_t a, uint32_t b2,
                                                          const float4 vv) {
@@ -474,7 +556,81 @@ __global__ void __launch_bounds__(BS) k_scatter_bin_w(const uint32_t* __restrict
 // histogram pass, the ~1M-entry scan and the runs of 16-64 records the binned path writes to scattered slots. Records,
 // their int64 sums and so the gradient are bitwise the binned paths' (the sum per entry is order-independent).
 constexpr uint32_t RT_STRIDE = SB_LEVEL_BUCKETS + 1;
-template <int BS>
+
+// One level's 8 corners for the whole wave - wave_run_sum of every corner, with the run structure of the wave worked out
+// once. The 8 corners of a level belong to one cell on every lane, so two adjacent lanes in one cell share all 8
+// entries and the corners' head masks are equal - except where adjacent lanes in different cells meet on one corner's
+// entry (a hash collision, the wrap of a dense level outside the unit cube). level_run_plan forms the level-local
+// entries e (corner_entries) and the 8 head masks; when they are equal (a wave-uniform test) it forms the run start,
+// the tail and the six step conditions once. corner_run_sums then applies each Kogge-Stone
+// step to the 16 partial sums of the 8 corners under its one condition (independent DPP adds in a row): per value
+// the adds and their order are wave_run_sum's.
+// When the masks differ each corner goes through wave_run_sum itself. Lanes without a sample carry entry 0xffffffff
+// and zero values and never emit, as there.
+struct RunPlan { bool same, none, tail, c[6]; };
+__device__ __forceinline__ RunPlan level_run_plan(const ScatterLevel& L, bool dense, bool ok, uint32_t e[8]) {
+	const uint32_t lane = threadIdx.x & 63;
+	corner_entries(L.s, dense, e);
+	uint64_t heads[8];
+#pragma unroll
+	for (uint32_t idx = 0; idx < 8; ++idx) {
+		if (!ok) e[idx] = 0xffffffffu;
+		heads[idx] = __ballot(dpp_u32<DPP_WAVE_SHR1>(~e[idx], e[idx]) != e[idx]);  // lane 0 keeps ~e: a head
+	}
+	RunPlan P;
+	P.same = true;
+#pragma unroll
+	for (uint32_t idx = 1; idx < 8; ++idx) P.same = P.same && heads[idx] == heads[0];
+	const uint64_t hd = heads[0];
+	P.none = hd == ~0ull;  // no run longer than one lane
+	// run start: the highest head at or below this lane (lane 0 is always one)
+	const uint32_t rs = 63u - (uint32_t)__clzll(hd & ((2ull << lane) - 1ull));
+	const uint32_t r0 = lane & ~15u;
+	P.c[0] = lane - r0 >= 1u && lane - 1u >= rs;
+	P.c[1] = lane - r0 >= 2u && lane - 2u >= rs;
+	P.c[2] = lane - r0 >= 4u && lane - 4u >= rs;
+	P.c[3] = lane - r0 >= 8u && lane - 8u >= rs;
+	P.c[4] = (r0 == 16u || r0 == 48u) && rs < r0;  // rows 1, 3 += the previous row's last lane
+	P.c[5] = lane >= 32u && rs < 32u;              // rows 2, 3 += lane 31
+	P.tail = lane == 63u || ((hd >> (lane + 1u)) & 1ull);
+	return P;
+}
+// the 8 corners' run-summed contributions, and bit idx set on the lane that emits corner idx's record
+__device__ __forceinline__ uint32_t corner_run_sums(const RunPlan& P, const ScatterLevel& L, bool ok, const uint32_t e[8], float a0[8], float a1[8]) {
+#pragma unroll
+	for (uint32_t k = 0; k < 8; ++k) {
+		corner_values(L, k, a0[k], a1[k]);
+		if (!ok) a0[k] = a1[k] = 0.f;
+	}
+	if (!P.same) {
+		uint32_t em = 0;
+#pragma unroll
+		for (uint32_t k = 0; k < 8; ++k) em |= wave_run_sum(e[k], a0[k], a1[k], ok) ? 1u << k : 0u;
+		return em;
+	}
+	const uint32_t all = 0xffu;
+	if (P.none) return ok ? all : 0u;
+#define NEUS_SEG_STEPG(CTRL, MASK, C)                                                                    \
+	if (__ballot(C)) {                                                                                   \
+		_Pragma("unroll") for (uint32_t k = 0; k < 8; ++k) {                                             \
+			const float t0 = dpp_f32<CTRL, MASK>(0.f, a0[k]), t1 = dpp_f32<CTRL, MASK>(0.f, a1[k]);      \
+			a0[k] = (C) ? a0[k] + t0 : a0[k];                                                            \
+			a1[k] = (C) ? a1[k] + t1 : a1[k];                                                            \
+		}                                                                                                \
+	}
+	NEUS_SEG_STEPG(DPP_ROW_SHR + 1, 0xf, P.c[0])
+	NEUS_SEG_STEPG(DPP_ROW_SHR + 2, 0xf, P.c[1])
+	NEUS_SEG_STEPG(DPP_ROW_SHR + 4, 0xf, P.c[2])
+	NEUS_SEG_STEPG(DPP_ROW_SHR + 8, 0xf, P.c[3])
+	NEUS_SEG_STEPG(DPP_BCAST15, 0xa, P.c[4])
+	NEUS_SEG_STEPG(DPP_BCAST31, 0xc, P.c[5])
+#undef NEUS_SEG_STEPG
+	return ok && P.tail ? all : 0u;
+}
+
+// DIRECT: corner entries by corner_entries and one run structure per level (level_run_plan); otherwise grid_index and
+// wave_run_sum per corner, as the binned paths.
+template <int BS, bool DIRECT>
 __global__ void __launch_bounds__(BS) k_scatter_bin_r(const uint32_t* __restrict__ n_ptr, uint32_t n_fixed, uint32_t ld,
                                                         const float* __restrict__ coords, uint32_t coord_stride, const GridLevels gl,
                                                         uint32_t valid_level, const uint32_t* __restrict__ dLdenc, const uint32_t* __restrict__ g,
@@ -487,9 +643,13 @@ __global__ void __launch_bounds__(BS) k_scatter_bin_r(const uint32_t* __restrict
 	const uint32_t i = blk * blockDim.x + threadIdx.x;
 	const bool ok = i < n;
 	const uint32_t ic = ok ? i : 0;
-	const float* c = coords + (size_t)ic * coord_stride;
-	const float x = c[0], y = c[1], z = c[2];
-	const float4 vv = v4[ic];
+	float x = 0.f, y = 0.f, z = 0.f;
+	float4 vv = make_float4(0.f, 0.f, 0.f, 0.f);
+	if constexpr (!DIRECT) {
+		const float* c = coords + (size_t)ic * coord_stride;
+		x = c[0]; y = c[1]; z = c[2];
+		vv = v4[ic];
+	}
 	const uint32_t n_lv = min(gl.n_levels, valid_level + 1);
 	// the level's two per-sample operands, loaded one level ahead (the level loop's barriers would otherwise expose
 	// their latency once per level); workgroup (chunk, y) bins levels y, y + gridDim.y, ... of its chunk
@@ -503,15 +663,40 @@ __global__ void __launch_bounds__(BS) k_scatter_bin_r(const uint32_t* __restrict
 		const bool few = size <= 4 * SB_SIZE;
 		for (uint32_t k = threadIdx.x; k < nlb; k += blockDim.x) cnt[k] = 0;
 		__syncthreads();
+		if constexpr (DIRECT) {
+			// Unlike a / g above, the position and v are loaded here, per level, behind an opaque index: held across the
+			// level loop they cost 6 of the registers that decide between two and three workgroups per CU (94 against 71
+			// VGPRs with the 24 entries and partial sums live), and occupancy is worth more to this kernel than the one
+			// exposed load (L2 hits; with the default one level per workgroup there is no second level to reload for)
+			uint32_t icl = ic;
+			asm volatile("" : "+v"(icl));
+			const float* c = coords + (size_t)icl * coord_stride;
+			x = c[0]; y = c[1]; z = c[2];
+			vv = v4[icl];
+		}
 		const ScatterLevel L = scatter_level_ab(gl, l, x, y, z, a_cur, g_cur, vv);
 		a_cur = a_next; g_cur = g_next;
 		uint32_t re[8], rs[8], rg[8];
+		uint32_t ce[8], em = 0;
+		float ca0[8], ca1[8];
+		if constexpr (DIRECT) {
+			const RunPlan rp = level_run_plan(L, (gl.dense_bits >> l) & 1u, ok, ce);
+			em = corner_run_sums(rp, L, ok, ce, ca0, ca1);
+		}
 #pragma unroll
 		for (uint32_t idx = 0; idx < 8; ++idx) {
-			uint32_t gidx; float a0, a1;
-			corner_contribution(L, idx, gidx, a0, a1);
-			const bool emit = wave_run_sum(gidx, a0, a1, ok);
-			const uint32_t e = gidx - off, lb = e >> SB_SHIFT;
+			uint32_t e; float a0, a1;
+			bool emit;
+			if constexpr (DIRECT) {
+				e = ce[idx]; a0 = ca0[idx]; a1 = ca1[idx];
+				emit = (em >> idx) & 1u;
+			} else {
+				uint32_t gidx;
+				corner_contribution(L, idx, gidx, a0, a1);
+				emit = wave_run_sum(gidx, a0, a1, ok);
+				e = gidx - off;
+			}
+			const uint32_t lb = e >> SB_SHIFT;
 			uint32_t sl = 0;
 			if (few) sl = wave_bucket_slot(cnt, lb, emit);
 			else if (emit) sl = atomicAdd(&cnt[lb], 1u);
@@ -882,13 +1067,46 @@ void launch_grid_ddx(hipStream_t s, uint32_t n, uint32_t ld, const float* coords
 	if (na) k_grid_ddx<<<dim3(gx, na), 256, 0, s>>>(n, ld, coords, gl, grid, (const uint32_t*)g, ddx, partial);
 	launch_grid_ddx_sum(s, n, na, partial, dLdx);
 }
+// Whether corner_entries (grid_common.h) equals grid_index on every level: a dense level whose in-cube corner indices
+// stay below twice its table, or a hashed one (grid_index's own stride test, in its u32 arithmetic) with a power-of-two
+// table. Any other table keeps grid_index. (A few integer operations per level, on the host, per launch.)
+uint32_t g_dbg_grid_generic = 0;
+static bool grid_levels_direct_index(const GridLevels& gl) {
+	if (g_dbg_grid_generic) return false;
+	for (uint32_t l = 0; l < gl.n_levels; ++l) {
+		const uint64_t r = gl.res[l], hs = gl.offset[l + 1] - gl.offset[l];
+		if (hs == 0) return false;
+		if ((gl.dense_bits >> l) & 1u) {
+			if (r * r * r > hs || r + r * r + r * r * r >= 2 * hs) return false;
+		} else {
+			uint32_t stride = gl.res[l];
+			if (stride <= hs) stride *= gl.res[l];
+			if (stride <= hs) stride *= gl.res[l];
+			if (!(hs < stride) || (hs & (hs - 1)) != 0) return false;
+		}
+	}
+	return true;
+}
+// k_grid_encode<true>'s 32-bit byte offsets: a level's enc row and six dy/dx rows, the coordinate records of ld samples
+// and every level table stay below 2^31 bytes (and 6 L ld below 2^31 elements)
+static bool encode_direct_ok(const GridLevels& gl, uint32_t ld, uint32_t coord_stride) {
+	if (!grid_levels_direct_index(gl)) return false;
+	const uint64_t lim = 1ull << 31;
+	if (6ull * gl.n_levels * ld >= lim || 24ull * ld >= lim || 4ull * ld * coord_stride >= lim) return false;
+	for (uint32_t l = 0; l < gl.n_levels; ++l)
+		if (4ull * (gl.offset[l + 1] - gl.offset[l]) >= lim) return false;
+	return true;
+}
 void launch_grid_encode(hipStream_t s, const uint32_t* n_ptr, uint32_t n_fixed, uint32_t ld, const float* coords, uint32_t coord_stride,
                         const GridLevels& gl, uint32_t valid_level, const half_t* grid, uint32_t* enc, float* dydx, uint32_t grid_x,
                         const EncodeRollover* ro) {
 	if (!grid_x) return;
 	const EncodeRollover r = ro ? *ro : EncodeRollover{nullptr, 0u, nullptr, nullptr};
 	dbg_lds_gate(s);
-	k_grid_encode<<<dim3(grid_x, gl.n_levels), 256, 0, s>>>(n_ptr, n_fixed, ld, coords, coord_stride, gl, valid_level, grid, enc, dydx, r);
+	if (encode_direct_ok(gl, ld, coord_stride))
+		k_grid_encode<true><<<dim3(grid_x, gl.n_levels), 256, 0, s>>>(n_ptr, n_fixed, ld, coords, coord_stride, gl, valid_level, grid, enc, dydx, r);
+	else
+		k_grid_encode<false><<<dim3(grid_x, gl.n_levels), 256, 0, s>>>(n_ptr, n_fixed, ld, coords, coord_stride, gl, valid_level, grid, enc, dydx, r);
 }
 size_t scatter_records_capacity(uint32_t n_cap, uint32_t n_levels) { return (size_t)n_cap * n_levels * 8; }
 std::vector<uint32_t> scatter_accum_jobs(const GridLevels& gl, uint32_t n_buckets, uint32_t& n_split) {
@@ -941,15 +1159,18 @@ void launch_grid_scatter(hipStream_t s, const uint32_t* n_ptr, uint32_t n_fixed,
 		const uint32_t n_lv = std::min(gl.n_levels, valid_level + 1);
 		const dim3 grid(w.n_chunks, w.level_groups ? std::min(w.level_groups, n_lv) : n_lv);
 		dbg_lds_gate(s);
-		if (w.chunk == 1024)
-			k_scatter_bin_r<1024><<<grid, 1024, 0, s>>>(n_ptr, n_fixed, ld, coords, coord_stride, gl, valid_level, (const uint32_t*)dLdenc,
-			                                            (const uint32_t*)g, v, w);
-		else if (w.chunk == 256)
-			k_scatter_bin_r<256><<<grid, 256, 0, s>>>(n_ptr, n_fixed, ld, coords, coord_stride, gl, valid_level, (const uint32_t*)dLdenc,
-			                                          (const uint32_t*)g, v, w);
-		else
-			k_scatter_bin_r<512><<<grid, 512, 0, s>>>(n_ptr, n_fixed, ld, coords, coord_stride, gl, valid_level, (const uint32_t*)dLdenc,
-			                                          (const uint32_t*)g, v, w);
+#define NEUS_BIN_R(BS, DIRECT) \
+	k_scatter_bin_r<BS, DIRECT><<<grid, BS, 0, s>>>(n_ptr, n_fixed, ld, coords, coord_stride, gl, valid_level, (const uint32_t*)dLdenc, (const uint32_t*)g, v, w)
+		if (grid_levels_direct_index(gl)) {
+			if (w.chunk == 1024) NEUS_BIN_R(1024, true);
+			else if (w.chunk == 256) NEUS_BIN_R(256, true);
+			else NEUS_BIN_R(512, true);
+		} else {
+			if (w.chunk == 1024) NEUS_BIN_R(1024, false);
+			else if (w.chunk == 256) NEUS_BIN_R(256, false);
+			else NEUS_BIN_R(512, false);
+		}
+#undef NEUS_BIN_R
 		const uint32_t n_act = std::min(valid_level + 1, gl.n_levels);
 		if (!split) {
 			const uint32_t nj = std::min(w.n_jobs2, w.jobs2_before[n_act]);

@@ -37,6 +37,37 @@ __device__ __forceinline__ void gather_corners(const LevelSetup& s, const half_t
 	}
 }
 
+// The 8 corner entries of one level without a division: e[idx] == grid_index(hsize, res, corner idx) for every input,
+// on a level the host has classified (grid_levels_direct_index, grid.hip; `dense` is the level's dense_bits bit, so the
+// branch is wave-uniform). The y and z terms are formed once for the four (y, z) pairs.
+//   hashed: the table size is a power of two, so `% hashmap_size` is a mask.
+//   dense:  a cell inside the unit cube has every coordinate <= res - 1, so a corner index is at most
+//           res + res^2 + res^3 < 2 hsize and one conditional subtract is the modulo. Cells outside it (negative ones
+//           wrap to huge unsigned values) take the true modulo, on the rare lanes that need it.
+__device__ __forceinline__ void corner_entries(const LevelSetup& s, bool dense, uint32_t e[8]) {
+	const uint32_t hs = s.hsize;
+	if (dense) {
+		const uint32_t rr = s.res * s.res;
+		const uint32_t y0 = s.g[1] * s.res, y1 = y0 + s.res, z0 = s.g[2] * rr, z1 = z0 + rr;
+		const uint32_t yz[4] = {y0 + z0, y1 + z0, y0 + z1, y1 + z1};
+		if (__builtin_expect(s.g[0] >= s.res || s.g[1] >= s.res || s.g[2] >= s.res, 0)) {
+#pragma unroll
+			for (uint32_t idx = 0; idx < 8; ++idx) e[idx] = (s.g[0] + (idx & 1) + yz[idx >> 1]) % hs;
+		} else {
+#pragma unroll
+			for (uint32_t idx = 0; idx < 8; ++idx) {
+				const uint32_t ed = s.g[0] + (idx & 1) + yz[idx >> 1];
+				e[idx] = min(ed, ed - hs);  // ed < 2 hs
+			}
+		}
+	} else {
+		const uint32_t y0 = s.g[1] * 2654435761u, y1 = y0 + 2654435761u, z0 = s.g[2] * 805459861u, z1 = z0 + 805459861u;
+		const uint32_t yz[4] = {y0 ^ z0, y1 ^ z0, y0 ^ z1, y1 ^ z1};
+#pragma unroll
+		for (uint32_t idx = 0; idx < 8; ++idx) e[idx] = ((s.g[0] + (idx & 1)) ^ yz[idx >> 1]) & (hs - 1u);
+	}
+}
+
 // Features: fp16 accumulation of fp16-rounded terms, as the reference (result[f] += (T)(weight * data)).
 __device__ __forceinline__ h2 interp_features(const LevelSetup& s, const h2 v[8]) {
 	half_t r0 = (half_t)0.f, r1 = (half_t)0.f;

@@ -2978,6 +2978,7 @@ int neus_debug_scan_giveup(void* stream, const uint32_t* in, uint32_t* out, uint
 int neus_debug_set_lds_fill(NeusTestbed* tb, uint32_t pattern) { return guard([&] { tb->dbg_lds_fill = pattern; }); }
 int neus_debug_set_lds_fill_all(NeusTestbed* tb, uint32_t pattern) { return guard([&] { tb->dbg_lds_fill_all = pattern; }); }
 int neus_debug_set_xcd_shift(NeusTestbed* tb, uint32_t n_blocks) { return guard([&] { tb->dbg_xcd_shift = n_blocks; }); }
+int neus_debug_set_grid_generic(uint32_t on) { return guard([&] { g_dbg_grid_generic = on; }); }
 // Diagnostic: `launches` launches of the fp32-denormal probe on a stream of its own (device `device`), each compared with
 // the CPU's bits; stats as debug_denorm_probe (march.hip)
 int neus_debug_denorm_probe(int device, uint32_t n, uint32_t launches, uint64_t* stats) {
