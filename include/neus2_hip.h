@@ -164,9 +164,9 @@ typedef struct NeusNetLayout {
  * version 3: NeusDataParallelInfo gained host_group; version 4: neus_module_create_encoding gained requested_precision;
  * version 5: neus_testbed_{set_,}exchange_timing, neus_host_group_create gained job_token; version 6: NeusTrainStats gained
  * march_cut_steps and march_cut_reruns; version 7: neus_module_backward_backward_input writes dL_ddLdoutput and dL_dinput for
- * every module kind (the network modules ignored both pointers before).
+ * every module kind (the network modules ignored both pointers before); version 8: neus_debug_mlp_train added.
  * Bindings compare it on load so that a stale library or binding fails loudly instead of misreading arguments. */
-#define NEUS_ABI_VERSION 7u
+#define NEUS_ABI_VERSION 8u
 int neus_abi_version(uint32_t* out);
 const char* neus_last_error(void);
 int neus_device_count(int* count);
@@ -350,6 +350,16 @@ int neus_debug_scatter_parts(NeusTestbed* tb, uint32_t* parts_per_level /* n_lev
 int neus_debug_grid_scatter(NeusTestbed* tb, void* hip_stream, uint32_t n_cap, const uint32_t* n_valid, const float* coords,
                             uint32_t coord_stride, uint32_t valid_level, const void* dLdenc, const void* genc, const float* v,
                             float* grid_grad_out);
+/* Test hook: the training MLP kernels alone (launch_mlp_train, both parts, then launch_mlp_grad_reduce) on caller-given
+ * device buffers; no encode and no grid scatter; synchronous. n: a positive multiple of 128, <= batch_size (else an error).
+ * coords n x 7 f32; enc [n_levels][n] half2 (neus_grid_encode's layout with ld = n) and dydx [6 n_levels][n] f32 stand in
+ * for the encode's outputs; dL_dout n x 16 fp16. grads_out: n_params f32, the five matrix blocks and the variance
+ * gradient written, everything else zero. Nullable outputs: dpos n float4 (dL/d position, first order), and the kernels'
+ * hand-off buffers copied out of the testbed: genc / dLdenc [n_levels][n] half2 (rows 3.. of W0^T G_h and of dL/d(density
+ * input): the grid scatter's operands), d1_delta [16][n] fp16, v n float4. */
+int neus_debug_mlp_train(NeusTestbed* tb, void* hip_stream, uint32_t n, const float* coords, const uint16_t* enc, const float* dydx,
+                         const uint16_t* dL_dout, uint32_t indeed_batch_size, float* grads_out, float* dpos, uint16_t* genc_out,
+                         uint16_t* dLdenc_out, uint16_t* d1_delta_out, float* v_out);
 /* Development check of the single-pass exclusive scan the step's compactions use (scan.hip): device buffers in / out
  * of n u32 on `hip_stream`, `reps` launches on one fresh state (the epoch re-arm), synchronous; failures = bounded-wait
  * give-ups (0 expected). */

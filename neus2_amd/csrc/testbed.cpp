@@ -2707,6 +2707,34 @@ int neus_debug_grid_scatter(NeusTestbed* tb, void* stream, uint32_t n_cap, const
 		HIP_CHECK(hipStreamSynchronize(s));
 	});
 }
+int neus_debug_mlp_train(NeusTestbed* tb, void* stream, uint32_t n, const float* coords, const uint16_t* enc, const float* dydx,
+                         const uint16_t* dL_dout, uint32_t indeed_batch_size, float* grads_out, float* dpos, uint16_t* genc_out,
+                         uint16_t* dLdenc_out, uint16_t* d1_delta_out, float* v_out) {
+	return guard([&] {
+		if (!tb->have_net) throw std::runtime_error("no network");
+		if (n == 0 || n % 128 != 0) throw std::runtime_error("neus_debug_mlp_train: n must be a positive multiple of 128");
+		if (n > tb->batch) throw std::runtime_error("neus_debug_mlp_train: n exceeds batch_size");
+		if (indeed_batch_size == 0) throw std::runtime_error("neus_debug_mlp_train: indeed_batch_size must be positive");
+		if (!coords || !enc || !dydx || !dL_dout || !grads_out) throw std::runtime_error("neus_debug_mlp_train: null buffer");
+		hipStream_t s = as_stream(tb, stream);
+		const Layout& l = tb->lay;
+		HIP_CHECK(hipMemsetAsync(grads_out, 0, (size_t)l.P * 4, s));
+		// the testbed's hand-off buffers with ld = n: rows [.][n] are contiguous, as the caller's
+		TrainBufs t = tb->tbuf;
+		t.indeed_batch = (float)indeed_batch_size;
+		t.dpos = (float4*)dpos;
+		t.var_grad = grads_out + l.var_off;
+		launch_mlp_train(s, l.L, l.W, nullptr, n, n, coords, (const half_t*)enc, dydx, (const half_t*)dL_dout, tb->mlp, t);
+		launch_mlp_grad_reduce(s, tb->grad_reduce(n, grads_out, nullptr));
+		HIP_CHECK(hipGetLastError());
+		const size_t pair = (size_t)l.L * n * 2 * sizeof(half_t);
+		if (genc_out) HIP_CHECK(hipMemcpyAsync(genc_out, t.genc, pair, hipMemcpyDeviceToDevice, s));
+		if (dLdenc_out) HIP_CHECK(hipMemcpyAsync(dLdenc_out, t.dLdenc, pair, hipMemcpyDeviceToDevice, s));
+		if (d1_delta_out) HIP_CHECK(hipMemcpyAsync(d1_delta_out, t.d1_delta, (size_t)16 * n * sizeof(half_t), hipMemcpyDeviceToDevice, s));
+		if (v_out) HIP_CHECK(hipMemcpyAsync(v_out, t.v, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+	});
+}
 int neus_debug_march_profile(NeusTestbed* tb, unsigned long long* out, uint32_t max_waves, uint32_t* n_waves) {
 	return guard([&] {
 		if (!tb->have_net) throw std::runtime_error("no network");

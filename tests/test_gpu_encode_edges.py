@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-import scatter_cases as SC
+from edge_positions import edge_positions
 from gpu_util import dev, host, ptr
 
 pytestmark = pytest.mark.gpu
@@ -40,24 +40,7 @@ def env(torch_cuda):
 
 
 def _positions(O, cfg):
-    _, res, scale, _ = O.grid_tables(cfg)
-    rng = np.random.default_rng(22)
-    parts = [rng.uniform(0.0, 1.0, (100, 3))]
-    for l in (0, 5, 13):
-        s, r = np.float64(scale[l]), int(res[l])
-        k = rng.integers(0, r, (32, 3)).astype(np.float64)
-        parts.append((k[:16] - 0.5) / s)  # fmaf(x, scale, 0.5) an integer: the boundary between two cells
-        parts.append(k[16:] / s)          # a vertex of the level
-        mixed = rng.uniform(0.0, 1.0, (8, 3))
-        mixed[:, l % 3] = (k[:8, 0] - 0.5) / s  # on a boundary along one axis only
-        parts.append(mixed)
-    parts.append(np.array([[(i >> d) & 1 for d in range(3)] for i in range(8)], np.float64))  # 0.0 and 1.0
-    parts.append(SC.OUTSIDE.astype(np.float64))
-    parts.append(np.float64([[-0.3, 0.5, 0.5], [1.7, 0.5, 0.5], [0.5, -0.3, 1.7], [1.7, 1.7, 1.7], [-0.3, -0.3, -0.3]]))
-    x = np.concatenate(parts)
-    x = np.concatenate([x, rng.uniform(-0.4, 1.4, (N - len(x), 3))]).astype(np.float32)
-    assert x.shape == (N, 3)
-    return x
+    return edge_positions(O, cfg, N)
 
 
 def _encode(env, valid):
