@@ -33,6 +33,11 @@
  *     neus_optimizer_step              Trainer::optimizer_step (Ema/ExpDecay/Adam)          trainer.h:170-172
  *     neus_occ_update                  Testbed::update_density_grid_nerf                    testbed_nerf.cu:3293-3397
  *
+ *   Rendering operators (stateless: no handle), the differentiable pieces between the networks and the pixel loss:
+ *     neus_volrend_march_count/_write  constant-step march through a byte occupancy grid into packed rays
+ *     neus_volrend_alpha_*             the NeuS SDF-to-alpha of compute_loss_kernel_train_nerf  testbed_nerf.cu:1475-1997
+ *     neus_volrend_composite_*         transmittance compositing with the T < t_stop cut, any 1..8 channels
+ *
  * Layouts (DESIGN.md §Data layout): coords AoS 7 x f32 (pos[3], dt, dir[3]) per sample;
  * network output / dL/doutput AoS 16 x fp16 per sample; params fp32 [P] in the reference's
  * set_params order [density MLP | rgb MLP | grid | variance(4)].
@@ -166,7 +171,7 @@ typedef struct NeusNetLayout {
  * march_cut_steps and march_cut_reruns; version 7: neus_module_backward_backward_input writes dL_ddLdoutput and dL_dinput for
  * every module kind (the network modules ignored both pointers before); version 8: neus_debug_mlp_train added.
  * Bindings compare it on load so that a stale library or binding fails loudly instead of misreading arguments. */
-#define NEUS_ABI_VERSION 8u
+#define NEUS_ABI_VERSION 9u
 int neus_abi_version(uint32_t* out);
 const char* neus_last_error(void);
 int neus_device_count(int* count);
@@ -633,6 +638,45 @@ int neus_fill_rollover(NeusTestbed* tb, void* stream, uint32_t n_elements, uint3
 int neus_occ_update(NeusTestbed* tb, void* stream, uint32_t n_uniform, uint32_t n_nonuniform);
 /* MFMA fragment-layout probe: C[32x32] = A[32x16] * B[16x32], fp16 row-major in, f32 out. */
 int neus_mfma_probe(const uint16_t* A, const uint16_t* B, float* C);
+
+/* ------------------------------------------------------------------ rendering operators (device buffers, no handle) */
+/* Stand-alone NeuS rendering over packed rays: no Testbed, no dataset. Every pointer is device memory, every launch
+ * goes on `stream` (null: the default stream) and returns without synchronising. Rays are packed: ranges [n_rays][2]
+ * int32 = (start, count), a ray's samples contiguous in [start, start + count); a range outside [0, n_samples) is
+ * treated as empty. No atomics: every output is bitwise repeatable.
+ *
+ * Occupancy march, two passes. Step k has t_k = t_min + ((float)k + 0.5f) * dt (one fp32 multiply, one add), the ray
+ * ends at the first t_k >= t_max (or after 2^24 steps), p = o + t_k * d; the step is kept when p lies in [0, 1)^3, the byte
+ * occupancy[((int)(p.z grid) * grid + (int)(p.y grid)) * grid + (int)(p.x grid)] is non-zero and fewer than max_per_ray
+ * steps of the ray were kept. grid: a power of two, 1..512. _count writes counts [n_rays]; the caller scans them into
+ * ranges; _write fills t [n_samples] and ray_idx [n_samples]. */
+int neus_volrend_march_count(void* stream, uint32_t n_rays, const float* rays_o, const float* rays_d, const float* t_min, const float* t_max,
+                             const uint8_t* occupancy, uint32_t grid, float dt, uint32_t max_per_ray, int32_t* counts);
+int neus_volrend_march_write(void* stream, uint32_t n_rays, const float* rays_o, const float* rays_d, const float* t_min, const float* t_max,
+                             const uint8_t* occupancy, uint32_t grid, float dt, uint32_t max_per_ray, const int32_t* ranges, uint32_t n_samples,
+                             float* t, int32_t* ray_idx);
+/* NeuS SDF-to-alpha (compute_loss_kernel_train_nerf's alpha): a1 = relu(0.5 - 0.5 cos), a2 = relu(-cos),
+ * iter_cos = -(a1 (1 - r) + a2 r), prev/next_sdf = sdf -/+ iter_cos dt / 2, c = sigmoid(prev_sdf inv_s),
+ * p = c - sigmoid(next_sdf inv_s), alpha = clamp((p + 1e-5) / (c + 1e-5), 0, 1). dt: [n] or null (then dt_value);
+ * inv_s: one device float or null (then inv_s_value). The backward recomputes from the inputs; g_inv_s (one float) is
+ * the fixed-order fp64 sum of per-block partials (partials: n_partials >= ceil(n / 256) doubles of scratch), rounded to fp32
+ * once; the backward evaluates in fp64. */
+int neus_volrend_alpha_forward(void* stream, uint32_t n, const float* sdf, const float* true_cos, const float* dt, float dt_value,
+                               const float* inv_s, float inv_s_value, float cos_anneal_ratio, float* alpha);
+int neus_volrend_alpha_backward(void* stream, uint32_t n, const float* sdf, const float* true_cos, const float* dt, float dt_value,
+                                const float* inv_s, float inv_s_value, float cos_anneal_ratio, const float* g_alpha, float* g_sdf,
+                                float* g_true_cos, double* partials, uint32_t n_partials, float* g_inv_s);
+/* Transmittance compositing. Per ray in sample order from T = 1: stop when T < t_stop; else w = alpha T, out += w v,
+ * opacity += w, T *= 1 - alpha. values [n_samples][n_channels], n_channels 1..8; out [n_rays][n_channels]; weights and
+ * trans [n_samples] (trans: T before the sample, the backward's saved state; both 0 from the stop on); n_composited
+ * [n_rays] = samples taken. Only samples inside a range are written. The backward takes cotangents of out, opacity and
+ * (nullable) weights: g_values = w g_out, g_alpha = T (G - B) with G = g_w + g_opacity + g_out . v and the reverse
+ * recurrence B_{i-1} = alpha_i G_i + (1 - alpha_i) B_i from B = 0 at the last sample taken (no division by 1 - alpha). */
+int neus_volrend_composite_forward(void* stream, uint32_t n_rays, uint32_t n_samples, uint32_t n_channels, const float* alpha, const float* values,
+                                   const int32_t* ranges, float t_stop, float* out, float* opacity, float* weights, float* trans, int32_t* n_composited);
+int neus_volrend_composite_backward(void* stream, uint32_t n_rays, uint32_t n_samples, uint32_t n_channels, const float* alpha, const float* values,
+                                    const int32_t* ranges, const float* trans, const int32_t* n_composited, const float* g_out,
+                                    const float* g_opacity, const float* g_weights, float* g_alpha, float* g_values);
 
 #ifdef __cplusplus
 }

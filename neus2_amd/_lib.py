@@ -130,10 +130,12 @@ EXPORTS = [
     "neus_module_initialize_params", "neus_module_inference", "neus_module_forward", "neus_module_backward",
     "neus_module_backward_backward_input",
     "neus_net_backward_pos", "neus_delta_apply", "neus_delta_backward",
+    "neus_volrend_march_count", "neus_volrend_march_write", "neus_volrend_alpha_forward", "neus_volrend_alpha_backward",
+    "neus_volrend_composite_forward", "neus_volrend_composite_backward",
 ]
 
 # include/neus2_hip.h's NEUS_ABI_VERSION this binding was written against: a library of another ABI fails to load
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _lib = None
 

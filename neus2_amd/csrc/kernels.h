@@ -557,4 +557,22 @@ void launch_bitfield(hipStream_t s, const float* grid, uint8_t* bitfield, const 
 // EMA of the grid + its cascade-0 mean (n multiple of 1024)
 void launch_ema_mean(hipStream_t s, uint32_t n, float decay, float* grid, const float* tmp, float* partial, float* mean);
 
+// Stand-alone rendering operators over packed rays (volrend.hip; the arguments are neus_volrend_*'s, include/neus2_hip.h).
+// Each validates its arguments on the host (std::runtime_error) before it launches.
+void launch_volrend_march_count(hipStream_t s, uint32_t n_rays, const float* rays_o, const float* rays_d, const float* t_min, const float* t_max,
+                                const uint8_t* occupancy, uint32_t grid, float dt, uint32_t max_per_ray, int32_t* counts);
+void launch_volrend_march_write(hipStream_t s, uint32_t n_rays, const float* rays_o, const float* rays_d, const float* t_min, const float* t_max,
+                                const uint8_t* occupancy, uint32_t grid, float dt, uint32_t max_per_ray, const int32_t* ranges, uint32_t n_samples,
+                                float* t, int32_t* ray_idx);
+void launch_volrend_alpha_forward(hipStream_t s, uint32_t n, const float* sdf, const float* true_cos, const float* dt, float dt_value,
+                                  const float* inv_s, float inv_s_value, float cos_anneal_ratio, float* alpha);
+void launch_volrend_alpha_backward(hipStream_t s, uint32_t n, const float* sdf, const float* true_cos, const float* dt, float dt_value,
+                                   const float* inv_s, float inv_s_value, float cos_anneal_ratio, const float* g_alpha, float* g_sdf,
+                                   float* g_true_cos, double* partials, uint32_t n_partials, float* g_inv_s);
+void launch_volrend_composite_forward(hipStream_t s, uint32_t n_rays, uint32_t n_samples, uint32_t n_channels, const float* alpha, const float* values,
+                                      const int32_t* ranges, float t_stop, float* out, float* opacity, float* weights, float* trans, int32_t* n_composited);
+void launch_volrend_composite_backward(hipStream_t s, uint32_t n_rays, uint32_t n_samples, uint32_t n_channels, const float* alpha, const float* values,
+                                       const int32_t* ranges, const float* trans, const int32_t* n_composited, const float* g_out,
+                                       const float* g_opacity, const float* g_weights, float* g_alpha, float* g_values);
+
 } // namespace neus

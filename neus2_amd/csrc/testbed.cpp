@@ -3212,6 +3212,43 @@ int neus_mfma_probe(const uint16_t* A, const uint16_t* B, float* C) {
 	});
 }
 
+// Rendering operators (volrend.hip): stateless, on the caller's stream; the launchers validate and throw.
+int neus_volrend_march_count(void* stream, uint32_t n_rays, const float* rays_o, const float* rays_d, const float* t_min, const float* t_max,
+                             const uint8_t* occupancy, uint32_t grid, float dt, uint32_t max_per_ray, int32_t* counts) {
+	return guard([&] { launch_volrend_march_count((hipStream_t)stream, n_rays, rays_o, rays_d, t_min, t_max, occupancy, grid, dt, max_per_ray, counts); });
+}
+int neus_volrend_march_write(void* stream, uint32_t n_rays, const float* rays_o, const float* rays_d, const float* t_min, const float* t_max,
+                             const uint8_t* occupancy, uint32_t grid, float dt, uint32_t max_per_ray, const int32_t* ranges, uint32_t n_samples,
+                             float* t, int32_t* ray_idx) {
+	return guard([&] { launch_volrend_march_write((hipStream_t)stream, n_rays, rays_o, rays_d, t_min, t_max, occupancy, grid, dt, max_per_ray, ranges, n_samples, t, ray_idx); });
+}
+int neus_volrend_alpha_forward(void* stream, uint32_t n, const float* sdf, const float* true_cos, const float* dt, float dt_value,
+                               const float* inv_s, float inv_s_value, float cos_anneal_ratio, float* alpha) {
+	return guard([&] { launch_volrend_alpha_forward((hipStream_t)stream, n, sdf, true_cos, dt, dt_value, inv_s, inv_s_value, cos_anneal_ratio, alpha); });
+}
+int neus_volrend_alpha_backward(void* stream, uint32_t n, const float* sdf, const float* true_cos, const float* dt, float dt_value,
+                                const float* inv_s, float inv_s_value, float cos_anneal_ratio, const float* g_alpha, float* g_sdf,
+                                float* g_true_cos, double* partials, uint32_t n_partials, float* g_inv_s) {
+	return guard([&] {
+		launch_volrend_alpha_backward((hipStream_t)stream, n, sdf, true_cos, dt, dt_value, inv_s, inv_s_value, cos_anneal_ratio, g_alpha, g_sdf, g_true_cos,
+		                              partials, n_partials, g_inv_s);
+	});
+}
+int neus_volrend_composite_forward(void* stream, uint32_t n_rays, uint32_t n_samples, uint32_t n_channels, const float* alpha, const float* values,
+                                   const int32_t* ranges, float t_stop, float* out, float* opacity, float* weights, float* trans, int32_t* n_composited) {
+	return guard([&] {
+		launch_volrend_composite_forward((hipStream_t)stream, n_rays, n_samples, n_channels, alpha, values, ranges, t_stop, out, opacity, weights, trans, n_composited);
+	});
+}
+int neus_volrend_composite_backward(void* stream, uint32_t n_rays, uint32_t n_samples, uint32_t n_channels, const float* alpha, const float* values,
+                                    const int32_t* ranges, const float* trans, const int32_t* n_composited, const float* g_out,
+                                    const float* g_opacity, const float* g_weights, float* g_alpha, float* g_values) {
+	return guard([&] {
+		launch_volrend_composite_backward((hipStream_t)stream, n_rays, n_samples, n_channels, alpha, values, ranges, trans, n_composited, g_out, g_opacity,
+		                                  g_weights, g_alpha, g_values);
+	});
+}
+
 } // extern "C"
 
 // ============================================================ tcnn-shaped operator modules (cpp_api.h:66-110)
