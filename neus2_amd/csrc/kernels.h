@@ -1,5 +1,5 @@
 // Host-callable launchers of the gfx950 kernels (defined in the .hip files) and the structs
-// shared between the host orchestration (testbed.cpp) and the kernels.
+// shared between the host orchestration (testbed.cpp, operators.cpp) and the kernels.
 #pragma once
 #include <functional>
 #include <vector>
