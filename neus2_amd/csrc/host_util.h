@@ -1,8 +1,10 @@
-// Host helpers shared by the host units (testbed.cpp, operators.cpp): the HIP error check, the owning device buffers and
-// the C-ABI's exception guard. What they rest on (the allocation debug state, the thread's last error) has its one
+// Host helpers shared by the host units (testbed.cpp, operators.cpp): the HIP error check, the owners of every HIP
+// resource (device buffers; streams, events and pinned memory as handle.h Handles, with the functions that create them)
+// and the C-ABI's exception guard. What they rest on (the allocation debug state, the thread's last error) has its one
 // definition in testbed.cpp.
 #pragma once
 #include "kernels.h"
+#include "handle.h"
 
 #include <exception>
 #include <stdexcept>
@@ -22,6 +24,9 @@ void dbg_poison(void* p, size_t bytes);
 template <class T> struct Dev {
 	T* p = nullptr;
 	size_t n = 0;
+	Dev() = default;
+	Dev(const Dev&) = delete;  // (a copy would free twice; ScanTemp inherits the deletion)
+	Dev& operator=(const Dev&) = delete;
 	void alloc(size_t k) {
 		if (k <= n && p) return;
 		release();
@@ -40,6 +45,22 @@ struct ScanTemp : Dev<uint8_t> {
 	void release() { if (p) scan_temp_release(p); Dev<uint8_t>::release(); }
 	~ScanTemp() { release(); }
 };
+
+// Owned streams (drained, then destroyed), events and pinned host memory: created only here, each throwing as HIP_CHECK
+inline void stream_drain_destroy(hipStream_t s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+template <class T> void pinned_free(T* p) { (void)hipHostFree((void*)p); }
+using Stream = Handle<hipStream_t, stream_drain_destroy>;
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+template <class T> using Pinned = Handle<T*, pinned_free<T>>;
+inline Stream make_stream(unsigned flags) { hipStream_t s = nullptr; HIP_CHECK(hipStreamCreateWithFlags(&s, flags)); return Stream(s); }
+inline Stream make_stream(unsigned flags, int priority) { hipStream_t s = nullptr; HIP_CHECK(hipStreamCreateWithPriority(&s, flags, priority)); return Stream(s); }
+inline Event make_event(unsigned flags = hipEventDefault) { hipEvent_t e = nullptr; HIP_CHECK(hipEventCreateWithFlags(&e, flags)); return Event(e); }
+inline void ensure_event(Event& e, unsigned flags = hipEventDefault) { if (!e) e = make_event(flags); }
+template <class T> Pinned<T> make_pinned(size_t n, unsigned flags = hipHostMallocDefault) {
+	void* p = nullptr;
+	HIP_CHECK(hipHostMalloc(&p, n * sizeof(T), flags));
+	return Pinned<T>((T*)p);
+}
 
 inline uint32_t next_multiple(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
 

@@ -54,6 +54,13 @@ thread_local std::string g_err;
 std::atomic<uint64_t> g_alloc_seq{0}, g_alloc_base{0};
 NeusAllocDebug g_alloc_dbg;
 
+// Every owner of a HIP resource is single: none copies (a copy would release twice); the handles move without throwing,
+// the device buffers do not move at all (nothing needs it)
+template <class T> constexpr bool no_copy = !std::is_copy_constructible_v<T> && !std::is_copy_assignable_v<T>;
+static_assert(no_copy<Dev<float>> && no_copy<ScanTemp> && no_copy<Stream> && no_copy<Event> && no_copy<Pinned<float>>);
+static_assert(std::is_nothrow_move_constructible_v<Stream> && std::is_nothrow_move_constructible_v<Event> &&
+              std::is_nothrow_move_constructible_v<Pinned<float>>);
+
 } // namespace
 
 void neus::set_last_error(const char* what) { g_err = what; }
@@ -151,11 +158,14 @@ struct NeusLocalGroup {
 struct NeusTestbed {
 	const NeusOptions opt = NeusOptions::from_env();  // the NEUS_* switches, read once: they hold for the testbed's life
 	int device = 0;
+	// The current stream: the testbed's own (stream_own) except while a module call runs on its caller's (operators.cpp
+	// StreamSwap writes it through Core::stream); only stream_own is ever drained for good or destroyed
+	Stream stream_own;
 	hipStream_t stream = nullptr;
 	// side stream of the backward: the weight-gradient GEMM runs there beside the grid scatter (disjoint inputs and
 	// outputs; both deterministic), forked from and joined back into the step's stream by events
-	hipStream_t aux_stream = nullptr;
-	hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+	Stream aux_stream;
+	Event ev_fork, ev_join;
 	// Lookahead (opt.lookahead): the next step's ray sampling (ray generation, march, march write, ray sort) issued on
 	// la_stream behind this step's counters (their stream: the step's, or the exchange stream with a group), beside its
 	// backward and optimizer, which read none of its outputs. At any world size; only between steps of one
@@ -176,19 +186,15 @@ struct NeusTestbed {
 		if (la_deferred && at >= la_at) { auto f = std::move(la_deferred); la_deferred = nullptr; f(); }
 	}
 	int main_prio = 0;  // the step's streams' priority (0: created without one; the communication stream follows it)
-	hipStream_t la_stream = nullptr;
-	hipEvent_t ev_la_start = nullptr, ev_la_done = nullptr;
+	Stream la_stream;
+	Event ev_la_start, ev_la_done;
 	// development (NEUS_LA_STAT=1): per lookahead, timing events around its sampling (la stream) and around the next
 	// step's wait for it (main stream); summed and printed at the end of each neus_testbed_train call
-	std::vector<hipEvent_t> la_stat_ev;
+	std::vector<Event> la_stat_ev;
 	size_t la_stat_used = 0;
 	hipEvent_t la_stat_next() {
-		if (la_stat_used == la_stat_ev.size()) {
-			hipEvent_t e;
-			HIP_CHECK(hipEventCreate(&e));
-			la_stat_ev.push_back(e);
-		}
-		return la_stat_ev[la_stat_used++];
+		if (la_stat_used == la_stat_ev.size()) la_stat_ev.push_back(make_event());
+		return la_stat_ev[la_stat_used++].get();
 	}
 	void la_stat_report() {
 		if (la_stat_used < 4) { la_stat_used = 0; return; }
@@ -198,9 +204,9 @@ struct NeusTestbed {
 		size_t n = 0;
 		for (size_t k = 0; k + 4 <= la_stat_used; k += 4, ++n) {
 			float a = 0, b = 0, c = 0;
-			HIP_CHECK(hipEventElapsedTime(&a, la_stat_ev[k + 2], la_stat_ev[k + 3]));
-			HIP_CHECK(hipEventElapsedTime(&b, la_stat_ev[k], la_stat_ev[k + 1]));
-			HIP_CHECK(hipEventElapsedTime(&c, la_stat_ev[k + 1], la_stat_ev[k + 2]));
+			HIP_CHECK(hipEventElapsedTime(&a, la_stat_ev[k + 2].get(), la_stat_ev[k + 3].get()));
+			HIP_CHECK(hipEventElapsedTime(&b, la_stat_ev[k].get(), la_stat_ev[k + 1].get()));
+			HIP_CHECK(hipEventElapsedTime(&c, la_stat_ev[k + 1].get(), la_stat_ev[k + 2].get()));
 			wait += a; dur += b; slack += c;
 		}
 		std::fprintf(stderr, "la_stat n=%zu wait_us=%.1f sampling_us=%.1f slack_us=%.1f\n", n, 1e3 * wait / n, 1e3 * dur / n, 1e3 * slack / n);
@@ -391,7 +397,7 @@ struct NeusTestbed {
 	bool force_full = false;      // the step being re-run marches every slot
 	Dev<uint32_t> occ_nu_key, occ_nu_list, occ_nu_bins;  // opt.occ_nu_sort: the occupancy-biased samples binned by their coarse cell
 	bool abort_direct = false;            // the last risky step's word comes through abort_word (one rank)
-	volatile uint32_t* abort_word = nullptr;  // host-coherent pinned word k_loss_grad stores the witness to (one rank)
+	Pinned<volatile uint32_t> abort_word;     // host-coherent pinned word k_loss_grad stores the witness to (one rank)
 	bool mc_hist[2] = {false, false};  // the march of the last issued step / of the one before it was cut
 	struct StepSnap {
 		uint32_t training_step = 0, canonical_step = 0, adam_step = 0, call_left = 0;
@@ -402,7 +408,7 @@ struct NeusTestbed {
 	};
 	StepSnap snap[2];             // the host's step state at the start of the last issued step / of the one before it
 	bool abort_pending = false;   // the last issued step's abort word is on its way to pinned[100] (ev_abort)
-	hipEvent_t ev_abort = nullptr, ev_abort_src = nullptr;
+	Event ev_abort, ev_abort_src;
 	uint64_t mcut_steps = 0, mcut_reruns = 0;
 	Dev<StepState> st_recount;
 	static bool occ_at(uint32_t cs) { const uint32_t n_prep = std::min(16u, std::max(1u, cs / 16u)); return cs % n_prep == 0; }
@@ -425,16 +431,16 @@ struct NeusTestbed {
 	float loss_scalar_ema = 0.f, last_loss = 0.f, ek_loss = 0.f, mask_loss = 0.f, ray_loss = 0.f;
 	uint32_t last_rays_with_samples = 0;
 	bool loss_ema_init = false;
-	float* pinned = nullptr;  // [0..3]: loss sum, ek sum, mask sum, grid mean; [32..47] render / mesh counts; [48]: the step scans'
+	Pinned<float> pinned;     // [0..3]: loss sum, ek sum, mask sum, grid mean; [32..47] render / mesh counts; [48]: the step scans'
 	                          // give-up count; [64..]: StepState copy
 	bool loss_pending = false;
-	hipEvent_t ev_loss = nullptr;  // after the logged step's readback copies (consume_loss waits on it, not on the stream)
+	Event ev_loss;  // after the logged step's readback copies (consume_loss waits on it, not on the stream)
 	// data parallel: RCCL communicator (production) or an in-process group
-	ncclComm_t comm = nullptr;
+	Handle<ncclComm_t, ncclCommDestroy> comm;
 	NeusLocalGroup* group = nullptr;
 	// cross-process host-staged group (hostgroup.h): every collective staged on comm_stream through a pinned buffer
 	NeusHostGroup* hgroup = nullptr;
-	uint8_t* hg_stage = nullptr;
+	Pinned<uint8_t> hg_stage;
 	size_t hg_stage_bytes = 0;
 	uint32_t rank = 0, world = 1;
 	// the exchange setting must be the same on every rank (the overlapped and grouped exchanges issue different
@@ -447,31 +453,30 @@ struct NeusTestbed {
 	// which the step's stream joins before the optimizer. Off (NEUS_EXCHANGE_OVERLAP=0, neus_testbed_set_exchange_overlap):
 	// one grouped exchange after the backward. Elementwise sums are the same either way (bitwise with two ranks).
 	bool exchange_overlap = opt.exchange_overlap;
-	hipStream_t comm_stream = nullptr;
-	hipEvent_t ev_x[16] = {};
+	Stream comm_stream;
+	Event ev_x[16];
 	uint32_t ev_x_n = 0;
-	hipEvent_t ev_xdone = nullptr;
+	Event ev_xdone;
 	bool x_pending = false;
 	static constexpr uint32_t X_GROUPS = 3;   // grid level groups of the overlapped exchange (~equal bytes at L=14)
 	// on comm_stream after the work queued so far on the step's stream (RCCL); the in-process group stages on the host
 	hipStream_t x_stream() {
 		if (!comm && !hgroup) return stream;
 		if (!comm_stream) {
-			if (main_prio) HIP_CHECK(hipStreamCreateWithPriority(&comm_stream, hipStreamNonBlocking, main_prio));
-			else HIP_CHECK(hipStreamCreateWithFlags(&comm_stream, hipStreamNonBlocking));
-			HIP_CHECK(hipEventCreateWithFlags(&ev_xdone, hipEventDisableTiming));
+			comm_stream = main_prio ? make_stream(hipStreamNonBlocking, main_prio) : make_stream(hipStreamNonBlocking);
+			ev_xdone = make_event(hipEventDisableTiming);
 		}
-		hipEvent_t& e = ev_x[ev_x_n++ % 16];
-		if (!e) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-		HIP_CHECK(hipEventRecord(e, stream));
-		HIP_CHECK(hipStreamWaitEvent(comm_stream, e, 0));
+		Event& e = ev_x[ev_x_n++ % 16];
+		ensure_event(e, hipEventDisableTiming);
+		HIP_CHECK(hipEventRecord(e.get(), stream));
+		HIP_CHECK(hipStreamWaitEvent(comm_stream.get(), e.get(), 0));
 		x_pending = true;
-		return comm_stream;
+		return comm_stream.get();
 	}
 	void x_join() {  // the step's stream waits for every exchange issued on comm_stream
 		if (!x_pending) return;
-		HIP_CHECK(hipEventRecord(ev_xdone, comm_stream));
-		HIP_CHECK(hipStreamWaitEvent(stream, ev_xdone, 0));
+		HIP_CHECK(hipEventRecord(ev_xdone.get(), comm_stream.get()));
+		HIP_CHECK(hipStreamWaitEvent(stream, ev_xdone.get(), 0));
 		x_pending = false;
 	}
 	// level groups of the overlapped exchange: the active levels cut where the cumulative parameter count passes 1/3, 2/3
@@ -499,9 +504,9 @@ struct NeusTestbed {
 	// Two sets of phase events (steps alternate), so reading one step's timings never idles the GPU:
 	// the step after it is already queued. The phase marks skip the system-scope release fence (it
 	// writes back and invalidates the caches, which would slow the kernel after every mark).
-	hipEvent_t ev[2][N_PHASES + 1] = {};
-	hipEvent_t ev_done[2] = {};
-	StepState* prof_st = nullptr;  // pinned, one StepState copy per event set
+	Event ev[2][N_PHASES + 1];
+	Event ev_done[2];
+	Pinned<StepState> prof_st;  // pinned, one StepState copy per event set
 	bool prof_pending[2] = {false, false};
 	int prof_par = 0;
 	double phase_ms[N_PHASES] = {};
@@ -520,22 +525,23 @@ struct NeusTestbed {
 			HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
 			main_prio = hi;
 			if (opt.main_prio) {
-				HIP_CHECK(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, hi));
-				HIP_CHECK(hipStreamCreateWithPriority(&aux_stream, hipStreamNonBlocking, hi));
+				stream_own = make_stream(hipStreamNonBlocking, hi);
+				aux_stream = make_stream(hipStreamNonBlocking, hi);
 			} else {
 				main_prio = 0;
-				HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-				HIP_CHECK(hipStreamCreateWithFlags(&aux_stream, hipStreamNonBlocking));
+				stream_own = make_stream(hipStreamNonBlocking);
+				aux_stream = make_stream(hipStreamNonBlocking);
 			}
+			stream = stream_own.get();
 		}
-		HIP_CHECK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-		HIP_CHECK(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
-		HIP_CHECK(hipEventCreateWithFlags(&ev_loss, hipEventDisableTiming));
-		HIP_CHECK(hipHostMalloc((void**)&pinned, 128 * sizeof(float)));
+		ev_fork = make_event(hipEventDisableTiming);
+		ev_join = make_event(hipEventDisableTiming);
+		ev_loss = make_event(hipEventDisableTiming);
+		pinned = make_pinned<float>(128);
 		for (auto& set : ev)
-			for (auto& e : set) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
-		for (auto& e : ev_done) HIP_CHECK(hipEventCreate(&e));
-		HIP_CHECK(hipHostMalloc((void**)&prof_st, 2 * sizeof(StepState)));
+			for (auto& e : set) e = make_event(hipEventDisableSystemFence);
+		for (auto& e : ev_done) e = make_event();
+		prof_st = make_pinned<StepState>(2);
 		st.alloc(1);
 		HIP_CHECK(hipMemset(st.p, 0, sizeof(StepState)));
 		// pcg32 jump-ahead table of the streams this Testbed draws from (pcg32{seed} / pcg32{next_uint()}: increment 3)
@@ -548,31 +554,14 @@ struct NeusTestbed {
 	static constexpr uint64_t PCG_INC = 3u;  // make_pcg32(s) = pcg32 stream 1: inc = (1 << 1) | 1
 	PcgJumpTable jump_table() const { return PcgJumpTable{pcg_tab.p, PCG_INC}; }
 	~NeusTestbed() {
-		if (stream) (void)hipStreamSynchronize(stream);
-		if (comm) ncclCommDestroy(comm);
-		for (auto& set : ev)
-			for (auto& e : set) if (e) (void)hipEventDestroy(e);
-		for (auto& e : ev_done) if (e) (void)hipEventDestroy(e);
-		if (prof_st) (void)hipHostFree(prof_st);
-		if (pinned) (void)hipHostFree(pinned);
-		if (abort_word) (void)hipHostFree((void*)abort_word);
-		if (aux_stream) { (void)hipStreamSynchronize(aux_stream); (void)hipStreamDestroy(aux_stream); }
-		if (la_stream) { (void)hipStreamSynchronize(la_stream); (void)hipStreamDestroy(la_stream); }
-		if (ev_la_start) (void)hipEventDestroy(ev_la_start);
-		if (ev_la_done) (void)hipEventDestroy(ev_la_done);
-		for (auto& e : ad_ev) if (e) (void)hipEventDestroy(e);
-		if (ad_done) (void)hipEventDestroy(ad_done);
-		for (auto& e : xt_ev) for (auto& x : e) if (x) (void)hipEventDestroy(x);
-		for (hipEvent_t e : la_stat_ev) (void)hipEventDestroy(e);
-		if (ev_fork) (void)hipEventDestroy(ev_fork);
-		if (ev_join) (void)hipEventDestroy(ev_join);
-		if (ev_loss) (void)hipEventDestroy(ev_loss);
-		if (comm_stream) { (void)hipStreamSynchronize(comm_stream); (void)hipStreamDestroy(comm_stream); }
-		if (hg_stage) (void)hipHostFree(hg_stage);
-		for (auto& e : ev_x) if (e) (void)hipEventDestroy(e);
-		if (ev_xdone) (void)hipEventDestroy(ev_xdone);
-		for (auto& e : it_ev) if (e) (void)hipEventDestroy(e);
-		if (stream) (void)hipStreamDestroy(stream);
+		// every stream of the testbed idle before anything is released: no queued work then reads an event, a pinned block or
+		// a device buffer, so the members (Dev buffers included) may go in any order, before or after the streams
+		for (hipStream_t q : {stream_own.get(), aux_stream.get(), la_stream.get(), comm_stream.get()})
+			if (q) (void)hipStreamSynchronize(q);
+		comm.reset();  // the communicator before any stream: it was issuing on the exchange stream or the step's
+		// the streams in the order they have always gone back to the runtime (it is not neutral to that, see the
+		// constructor): by these explicit resets, declaration order would give comm, la, aux, step
+		aux_stream.reset(); la_stream.reset(); comm_stream.reset(); stream_own.reset();
 	}
 
 	// ------------------------------------------------------------ dataset (load_nerf, testbed_nerf.cu:2964-3095)
@@ -1074,7 +1063,7 @@ struct NeusTestbed {
 	void allreduce_f32(float* p, size_t n, bool max_op = false, hipStream_t on = nullptr) {
 		if (!coll_on() || n == 0) return;
 		++coll_calls; coll_bytes += n * 4; coll_bytes_step += n * 4;
-		if (comm) NCCL_CHECK(ncclAllReduce(p, p, n, ncclFloat32, max_op ? ncclMax : ncclSum, comm, on ? on : stream));
+		if (comm) NCCL_CHECK(ncclAllReduce(p, p, n, ncclFloat32, max_op ? ncclMax : ncclSum, comm.get(), on ? on : stream));
 		else if (hgroup) hg_allreduce(p, n * 4, NeusHostGroup::F32, max_op ? NeusHostGroup::MAX : NeusHostGroup::SUM, on);
 		else if (group) group->allreduce<float>(rank, p, n, max_op ? NeusLocalGroup::MAX : NeusLocalGroup::SUM, stream);
 		else throw std::runtime_error("data parallel: no communicator");
@@ -1082,7 +1071,7 @@ struct NeusTestbed {
 	void allreduce_u32(uint32_t* p, size_t n, hipStream_t on = nullptr) {
 		if (!coll_on() || n == 0) return;
 		++coll_calls; coll_bytes += n * 4; coll_bytes_step += n * 4;
-		if (comm) NCCL_CHECK(ncclAllReduce(p, p, n, ncclUint32, ncclSum, comm, on ? on : stream));
+		if (comm) NCCL_CHECK(ncclAllReduce(p, p, n, ncclUint32, ncclSum, comm.get(), on ? on : stream));
 		else if (hgroup) hg_allreduce(p, n * 4, NeusHostGroup::U32, NeusHostGroup::SUM, on);
 		else if (group) group->allreduce<uint32_t>(rank, p, n, NeusLocalGroup::SUM, stream);
 		else throw std::runtime_error("data parallel: no communicator");
@@ -1091,22 +1080,23 @@ struct NeusTestbed {
 	// device. Issued from the step's stream (on == nullptr / stream), it is gated after the work queued there and the step's
 	// stream waits for it; issued on comm_stream (the overlapped exchange), the stream order is the gate.
 	void hg_allreduce(void* dev, size_t bytes, uint32_t type, uint32_t op, hipStream_t on) {
-		const bool own = !(on && on == comm_stream);
+		const bool own = !(on && on == comm_stream.get());
 		hipStream_t cs = own ? x_stream() : on;
 		if (bytes > hg_stage_bytes) {  // grow: the queued collectives still read the old stage
-			if (comm_stream) HIP_CHECK(hipStreamSynchronize(comm_stream));
-			if (hg_stage) HIP_CHECK(hipHostFree(hg_stage));
+			if (comm_stream) HIP_CHECK(hipStreamSynchronize(comm_stream.get()));
+			hg_stage.reset();  // (freed before the larger one is allocated)
+			hg_stage_bytes = 0;
+			hg_stage = make_pinned<uint8_t>(std::max(bytes, (size_t)1 << 20));
 			hg_stage_bytes = std::max(bytes, (size_t)1 << 20);
-			HIP_CHECK(hipHostMalloc((void**)&hg_stage, hg_stage_bytes));
 		}
-		HIP_CHECK(hipMemcpyAsync(hg_stage, dev, bytes, hipMemcpyDeviceToHost, cs));
-		HostCollCall* c = new HostCollCall{hgroup, hg_stage, bytes, type, op};
+		HIP_CHECK(hipMemcpyAsync(hg_stage.get(), dev, bytes, hipMemcpyDeviceToHost, cs));
+		auto c = std::make_unique<HostCollCall>(HostCollCall{hgroup, hg_stage.get(), bytes, type, op});
 		HIP_CHECK(hipLaunchHostFunc(cs, [](void* a) {
-			HostCollCall* c = (HostCollCall*)a;
+			std::unique_ptr<HostCollCall> c((HostCollCall*)a);
 			c->g->allreduce_host(c->host, c->bytes, c->type, c->op);
-			delete c;
-		}, c));
-		HIP_CHECK(hipMemcpyAsync(dev, hg_stage, bytes, hipMemcpyHostToDevice, cs));
+		}, c.get()));
+		(void)c.release();  // the queued host function owns it from here
+		HIP_CHECK(hipMemcpyAsync(dev, hg_stage.get(), bytes, hipMemcpyHostToDevice, cs));
 		if (own) x_join();
 	}
 	// every rank must run the same exchange (overlapped or grouped): sum of the setting over the ranks is 0 or world
@@ -1235,19 +1225,19 @@ struct NeusTestbed {
 	// would be a fifth HIP stream of the process over GPU_MAX_HW_QUEUES = 4 hardware queues and share one - measured
 	// 1.12 -> 1.99 ms/step when it landed behind the lookahead's low-priority march (profiles/r06b_adam_overlap_mlp_grid_ab.txt)
 	hipStream_t ad_stream = nullptr;
-	hipEvent_t ad_ev[8] = {}, ad_done = nullptr;
+	Event ad_ev[8], ad_done;
 	int ad_n = 0;
 	void adam_issue(AdamSplit& a, uint32_t hi, const float* g, bool with_tr) {
 		if (!ad_stream) {
-			ad_stream = aux_stream;
-			for (auto& e : ad_ev) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-			HIP_CHECK(hipEventCreateWithFlags(&ad_done, hipEventDisableTiming));
+			ad_stream = aux_stream.get();
+			for (auto& e : ad_ev) e = make_event(hipEventDisableTiming);
+			ad_done = make_event(hipEventDisableTiming);
 		}
 		hi = hi >= lay.P ? lay.P : hi / 4 * 4;
 		if (hi <= a.next) return;
 		hipStream_t on = a.on;
 		if (!on) {
-			hipEvent_t e = ad_ev[ad_n++ % 8];
+			hipEvent_t e = ad_ev[ad_n++ % 8].get();
 			HIP_CHECK(hipEventRecord(e, stream));
 			HIP_CHECK(hipStreamWaitEvent(ad_stream, e, 0));
 			on = ad_stream;
@@ -1260,8 +1250,8 @@ struct NeusTestbed {
 	void adam_join(AdamSplit& a, const float* g) {
 		adam_issue(a, lay.P, g, false);  // (whatever is left: the levels past the valid one, the variance)
 		if (!a.on) {  // (on the exchange stream the step's x_join has waited for every piece already)
-			HIP_CHECK(hipEventRecord(ad_done, ad_stream));
-			HIP_CHECK(hipStreamWaitEvent(stream, ad_done, 0));
+			HIP_CHECK(hipEventRecord(ad_done.get(), ad_stream));
+			HIP_CHECK(hipStreamWaitEvent(stream, ad_done.get(), 0));
 		}
 		if (a.p.skip_ema_h) ema_h_stale = true;
 	}
@@ -1318,7 +1308,7 @@ struct NeusTestbed {
 	void mark(int i) {
 		static const char* const names[N_PHASES] = {"neus:occupancy", "neus:march", "neus:inference", "neus:loss", "neus:encode",
 		                                            "neus:mlp", "neus:wgrad", "neus:scatter", "neus:exchange", "neus:optimizer"};
-		if (profiling) HIP_CHECK(hipEventRecord(ev[prof_par][i], stream));
+		if (profiling) HIP_CHECK(hipEventRecord(ev[prof_par][i].get(), stream));
 		if (rx_open >= 0) roctxRangePop();
 		rx_open = i < N_PHASES ? i : -1;
 		if (rx_open >= 0) roctxRangePushA(names[i]);
@@ -1330,24 +1320,23 @@ struct NeusTestbed {
 	// passes only, never the bench's timed region)
 	bool infer_timing = false;
 	static constexpr int IT_MAX = 16;
-	hipEvent_t it_ev[2 * IT_MAX] = {};
+	Event it_ev[2 * IT_MAX];
 	int it_n = 0;
 	double it_ms = 0.0;
 	uint64_t it_launches = 0, it_steps = 0;
 	void it_arm() {
 		if (!infer_timing || it_n + 2 > 2 * IT_MAX) return;
-		for (int k = 0; k < 2; ++k)
-			if (!it_ev[it_n + k]) HIP_CHECK(hipEventCreate(&it_ev[it_n + k]));
-		g_infer_ev[0] = it_ev[it_n];
-		g_infer_ev[1] = it_ev[it_n + 1];
+		for (int k = 0; k < 2; ++k) ensure_event(it_ev[it_n + k]);
+		g_infer_ev[0] = it_ev[it_n].get();
+		g_infer_ev[1] = it_ev[it_n + 1].get();
 		it_n += 2;
 	}
 	void it_collect() {
 		if (!infer_timing || it_n < 2) { it_n = 0; return; }
-		HIP_CHECK(hipEventSynchronize(it_ev[it_n - 1]));
+		HIP_CHECK(hipEventSynchronize(it_ev[it_n - 1].get()));
 		for (int i = 0; i + 1 < it_n; i += 2) {
 			float ms = 0.f;
-			HIP_CHECK(hipEventElapsedTime(&ms, it_ev[i], it_ev[i + 1]));
+			HIP_CHECK(hipEventElapsedTime(&ms, it_ev[i].get(), it_ev[i + 1].get()));
 			it_ms += ms;
 			++it_launches;
 		}
@@ -1362,25 +1351,24 @@ struct NeusTestbed {
 	// ring wraps, the host running at most 16 steps ahead), so timing runs inside timed regions without a per-step sync.
 	bool xt_on = false;
 	static constexpr int XT_RING = 64;
-	hipEvent_t xt_ev[XT_RING][3] = {};  // [loss end (step stream), backward done (step stream), exchange done (exchange stream)]
+	Event xt_ev[XT_RING][3];  // [loss end (step stream), backward done (step stream), exchange done (exchange stream)]
 	int xt_head = 0, xt_n = 0;
 	double xt_exposed_ms = 0.0, xt_span_ms = 0.0;
 	uint64_t xt_steps = 0;
-	hipEvent_t* xt_slot() {
+	Event* xt_slot() {
 		if (xt_n == XT_RING) xt_collect_one();
-		hipEvent_t* e = xt_ev[(xt_head + xt_n) % XT_RING];
-		for (int k = 0; k < 3; ++k)
-			if (!e[k]) HIP_CHECK(hipEventCreate(&e[k]));
+		Event* e = xt_ev[(xt_head + xt_n) % XT_RING];
+		for (int k = 0; k < 3; ++k) ensure_event(e[k]);
 		++xt_n;
 		return e;
 	}
 	void xt_collect_one() {
-		hipEvent_t* e = xt_ev[xt_head];
-		HIP_CHECK(hipEventSynchronize(e[2]));
-		HIP_CHECK(hipEventSynchronize(e[1]));
+		Event* e = xt_ev[xt_head];
+		HIP_CHECK(hipEventSynchronize(e[2].get()));
+		HIP_CHECK(hipEventSynchronize(e[1].get()));
 		float exposed = 0.f, span = 0.f;
-		HIP_CHECK(hipEventElapsedTime(&exposed, e[1], e[2]));
-		HIP_CHECK(hipEventElapsedTime(&span, e[0], e[2]));
+		HIP_CHECK(hipEventElapsedTime(&exposed, e[1].get(), e[2].get()));
+		HIP_CHECK(hipEventElapsedTime(&span, e[0].get(), e[2].get()));
 		xt_exposed_ms += std::max(0.f, exposed);
 		xt_span_ms += span;
 		++xt_steps;
@@ -1441,9 +1429,9 @@ struct NeusTestbed {
 			for (uint32_t i = 1; i < MARCH_ITER;) {
 				launch_render_compact(s, n_alive, r_rays[cur].p, r_flags.p, r_base.p, r_rays[cur ^ 1].p, r_alive.p, r_scan_tmp.p, r_scan_bytes);
 				cur ^= 1;
-				HIP_CHECK(hipMemcpyAsync(pinned + 32, r_alive.p, 4, hipMemcpyDeviceToHost, s));
+				HIP_CHECK(hipMemcpyAsync(pinned.get() + 32, r_alive.p, 4, hipMemcpyDeviceToHost, s));
 				HIP_CHECK(hipStreamSynchronize(s));
-				std::memcpy(&n_alive, pinned + 32, 4);
+				std::memcpy(&n_alive, pinned.get() + 32, 4);
 				if (n_alive == 0) break;
 				const uint32_t n_steps = std::min(MAX_STEPS_INBETWEEN_COMPACTION, std::max(1u, n / n_alive));
 				launch_render_gen(s, n_alive, n_steps, ds, bitfield.p, bf_lin.p, r_rays[cur].p, r_coords.p);
@@ -1505,12 +1493,12 @@ struct NeusTestbed {
 		launch_exclusive_scan(s, mc_scan_tmp.p, mc_scan_bytes, cv, ov, nc);
 		launch_exclusive_scan(s, mc_scan_tmp.p, mc_scan_bytes, ct, ot, nc);
 		uint32_t last[4];
-		HIP_CHECK(hipMemcpyAsync(pinned + 40, cv + nc - 1, 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipMemcpyAsync(pinned + 41, ct + nc - 1, 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipMemcpyAsync(pinned + 42, ov + nc - 1, 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipMemcpyAsync(pinned + 43, ot + nc - 1, 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipMemcpyAsync(pinned.get() + 40, cv + nc - 1, 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipMemcpyAsync(pinned.get() + 41, ct + nc - 1, 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipMemcpyAsync(pinned.get() + 42, ov + nc - 1, 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipMemcpyAsync(pinned.get() + 43, ot + nc - 1, 4, hipMemcpyDeviceToHost, s));
 		HIP_CHECK(hipStreamSynchronize(s));
-		std::memcpy(last, pinned + 40, 16);
+		std::memcpy(last, pinned.get() + 40, 16);
 		const uint64_t nv = (uint64_t)last[2] + last[0], nt = (uint64_t)last[3] + last[1];
 		if (nv >= (1ull << 32) || 3 * nt >= (1ull << 32)) throw std::runtime_error("marching_cubes: mesh exceeds 32-bit indices");
 		mesh_v.alloc(3 * std::max<uint64_t>(nv, 1));
@@ -1548,6 +1536,12 @@ struct NeusTestbed {
 		if (abort_pending) check_abort();
 		train_step_body();
 	}
+	// The witness word (64 B, allocated at the first step that needs it) set to the sentinel for the step being issued
+	uint32_t* arm_abort_word() {
+		if (!abort_word) abort_word = make_pinned<volatile uint32_t>(16, hipHostMallocCoherent | hipHostMallocMapped);
+		*abort_word.get() = ~0u;
+		return (uint32_t*)abort_word.get();
+	}
 	// The last issued step's march-cut witness (opt.march_cut): when it aborted, its state changes were withheld on the
 	// device; the host state goes back to its start and the step runs again with the full march.
 	void check_abort() {
@@ -1556,18 +1550,18 @@ struct NeusTestbed {
 		if (abort_direct) {
 			// one rank: k_loss_grad stored the word to host-coherent memory (sentinel ~0 before the step): poll it, and
 			// after a bounded spin wait for the step's stream (the kernel has then run)
-			const volatile uint32_t* w = abort_word;
+			const volatile uint32_t* w = abort_word.get();
 			for (uint32_t k = 0; k < (1u << 22) && *w == ~0u; ++k) __builtin_ia32_pause();
 			if (*w == ~0u) HIP_CHECK(hipStreamSynchronize(stream));
 			a = *w;
 			if (a == ~0u) throw std::runtime_error("march cut: the witness word was not written");
 		} else {
-			HIP_CHECK(hipEventSynchronize(ev_abort));
-			std::memcpy(&a, pinned + 100, 4);
+			HIP_CHECK(hipEventSynchronize(ev_abort.get()));
+			std::memcpy(&a, pinned.get() + 100, 4);
 		}
 		if (!a) return;
 		// this testbed's streams drained (not the device's: another rank of an in-process group may share it)
-		for (hipStream_t q : {stream, aux_stream, la_stream, comm_stream})
+		for (hipStream_t q : {stream_own.get(), aux_stream.get(), la_stream.get(), comm_stream.get()})
 			if (q) HIP_CHECK(hipStreamSynchronize(q));
 		la_pending = false;
 		la_deferred = nullptr;
@@ -1658,7 +1652,7 @@ struct NeusTestbed {
 			if (canonical_step % n_prep == 0) throw std::runtime_error("train: lookahead issued before an occupancy update");
 			++la_steps;
 			if (opt.la_stat && la_stat_used % 4 == 2) HIP_CHECK(hipEventRecord(la_stat_next(), s));
-			HIP_CHECK(hipStreamWaitEvent(s, ev_la_done, 0));  // this step's samples came from the previous step's lookahead
+			HIP_CHECK(hipStreamWaitEvent(s, ev_la_done.get(), 0));  // this step's samples came from the previous step's lookahead
 			if (opt.la_stat && la_stat_used % 4 == 3) HIP_CHECK(hipEventRecord(la_stat_next(), s));
 		}
 		const bool cut = la_have ? la_cut : cut_for(training_step, progressive, call_left == 0, dyn);
@@ -1683,13 +1677,7 @@ struct NeusTestbed {
 		lp.abort_w = cutw.p + CW_ABORT; lp.abort_slot = training_step & 1u;
 		if (risky && !coll_on()) {
 			// one rank: the word goes straight from k_loss_grad to host memory (no copy, no event on the step's streams)
-			if (!abort_word) {
-				void* p = nullptr;
-				HIP_CHECK(hipHostMalloc(&p, 64, hipHostMallocCoherent | hipHostMallocMapped));
-				abort_word = (volatile uint32_t*)p;
-			}
-			*abort_word = ~0u;
-			lp.abort_host = (uint32_t*)abort_word;
+			lp.abort_host = arm_abort_word();
 		}
 		lp.dbg_fence = opt.dbg_loss_fence ? 1u : 0u;
 		const LossWork w = loss_work(base.p);
@@ -1773,8 +1761,8 @@ struct NeusTestbed {
 		const bool xo = coll_on() && exchange_overlap && (!dyn || train_canonical);
 		coll_bytes_step = 0;
 		hipStream_t cs = s;  // the stream the counters (and the lookahead's start) are ordered on
-		hipEvent_t* xt = coll_on() && xt_on ? xt_slot() : nullptr;
-		if (xt) HIP_CHECK(hipEventRecord(xt[0], s));
+		Event* xt = coll_on() && xt_on ? xt_slot() : nullptr;
+		if (xt) HIP_CHECK(hipEventRecord(xt[0].get(), s));
 		if (coll_on()) {
 			cs = xo ? x_stream() : stream;
 			coll_begin();
@@ -1798,26 +1786,20 @@ struct NeusTestbed {
 		// behind the exchange (a system-scope store, as k_loss_grad's at one rank); otherwise by a copy and an event
 		uint32_t* abort_host_ctr = nullptr;
 		if (risky && coll_on() && la_go) {
-			if (!abort_word) {
-				void* p = nullptr;
-				HIP_CHECK(hipHostMalloc(&p, 64, hipHostMallocCoherent | hipHostMallocMapped));
-				abort_word = (volatile uint32_t*)p;
-			}
-			*abort_word = ~0u;
-			abort_host_ctr = (uint32_t*)abort_word;
+			abort_host_ctr = arm_abort_word();
 			abort_direct = true;
 		}
 		if (risky && !abort_direct) {
 			// the all-reduced abort word to the host, off the step's stream (the backward starts at once)
 			if (!ev_abort) {
-				HIP_CHECK(hipEventCreateWithFlags(&ev_abort, hipEventDisableTiming));
-				HIP_CHECK(hipEventCreateWithFlags(&ev_abort_src, hipEventDisableTiming));
+				ev_abort = make_event(hipEventDisableTiming);
+				ev_abort_src = make_event(hipEventDisableTiming);
 			}
-			HIP_CHECK(hipEventRecord(ev_abort_src, cs));
-			HIP_CHECK(hipStreamWaitEvent(aux_stream, ev_abort_src, 0));
-			*(volatile uint32_t*)(pinned + 100) = ~0u;
-			HIP_CHECK(hipMemcpyAsync(pinned + 100, &st.p->cut_abort, 4, hipMemcpyDeviceToHost, aux_stream));
-			HIP_CHECK(hipEventRecord(ev_abort, aux_stream));
+			HIP_CHECK(hipEventRecord(ev_abort_src.get(), cs));
+			HIP_CHECK(hipStreamWaitEvent(aux_stream.get(), ev_abort_src.get(), 0));
+			*(volatile uint32_t*)(pinned.get() + 100) = ~0u;
+			HIP_CHECK(hipMemcpyAsync(pinned.get() + 100, &st.p->cut_abort, 4, hipMemcpyDeviceToHost, aux_stream.get()));
+			HIP_CHECK(hipEventRecord(ev_abort.get(), aux_stream.get()));
 			abort_pending = true;
 		}
 		{
@@ -1825,7 +1807,7 @@ struct NeusTestbed {
 				// the host's StepState readback first (its place in the step without the lookahead: nothing it reads is
 				// written between here and there - the ranks' counts are already summed), then the step counters the next
 				// step's sampling reads; both behind the counters' exchange (cs)
-				if (get_loss) HIP_CHECK(hipMemcpyAsync(pinned + 64, st.p, sizeof(StepState), hipMemcpyDeviceToHost, cs));
+				if (get_loss) HIP_CHECK(hipMemcpyAsync(pinned.get() + 64, st.p, sizeof(StepState), hipMemcpyDeviceToHost, cs));
 				launch_step_counters(cs, st.p, batch, max_samples, world, cfg.fixed_rays_per_batch, sca.eval_cnt, sca.n_eval, abort_host_ctr);
 				counters_done = true;
 				if (!la_stream) {
@@ -1835,13 +1817,12 @@ struct NeusTestbed {
 					const int want = opt.la_prio;
 					int lo = 0, hi = 0;
 					HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));  // (lo: least urgent, hi: most urgent; hi <= lo numerically)
-					if (want == 0) HIP_CHECK(hipStreamCreateWithFlags(&la_stream, hipStreamNonBlocking));
-					else HIP_CHECK(hipStreamCreateWithPriority(&la_stream, hipStreamNonBlocking, want > 0 ? hi : lo));
+					la_stream = want == 0 ? make_stream(hipStreamNonBlocking) : make_stream(hipStreamNonBlocking, want > 0 ? hi : lo);
 					// (device-side hand-offs between the step's and the lookahead's kernels: no system-scope fence - its
 					// L2 write-back held the step's stream ~6 us at the record; opt.ev_sysfence keeps it, for A/B)
 					const unsigned fl = hipEventDisableTiming | (opt.ev_sysfence ? 0u : hipEventDisableSystemFence);
-					HIP_CHECK(hipEventCreateWithFlags(&ev_la_start, fl));
-					HIP_CHECK(hipEventCreateWithFlags(&ev_la_done, fl));
+					ev_la_start = make_event(fl);
+					ev_la_done = make_event(fl);
 				}
 				if (!scan_tmp_la.p || scan_tmp_la.n < scan_tmp_bytes + 256) {
 					scan_tmp_la.alloc(scan_tmp_bytes + 256);
@@ -1855,12 +1836,13 @@ struct NeusTestbed {
 				const bool cut1 = la_cut, mcut1 = la_mcut;
 				la_at = mcut1 ? opt.la_at_cut : opt.la_at_full;
 				la_deferred = [this, cs, dp, r1, prog1, cut1, mcut1] {
-					HIP_CHECK(hipEventRecord(ev_la_start, cs));
-					HIP_CHECK(hipStreamWaitEvent(la_stream, ev_la_start, 0));
-					if (opt.la_stat) { la_stat_used -= la_stat_used % 4; HIP_CHECK(hipEventRecord(la_stat_next(), la_stream)); }
-					issue_march(la_stream, dp, r1, prog1, scan_tmp_la.p, cut1, mcut1);
-					if (opt.la_stat) HIP_CHECK(hipEventRecord(la_stat_next(), la_stream));
-					HIP_CHECK(hipEventRecord(ev_la_done, la_stream));
+					hipStream_t ls = la_stream.get();
+					HIP_CHECK(hipEventRecord(ev_la_start.get(), cs));
+					HIP_CHECK(hipStreamWaitEvent(ls, ev_la_start.get(), 0));
+					if (opt.la_stat) { la_stat_used -= la_stat_used % 4; HIP_CHECK(hipEventRecord(la_stat_next(), ls)); }
+					issue_march(ls, dp, r1, prog1, scan_tmp_la.p, cut1, mcut1);
+					if (opt.la_stat) HIP_CHECK(hipEventRecord(la_stat_next(), ls));
+					HIP_CHECK(hipEventRecord(ev_la_done.get(), ls));
 				};
 				if (cs != s) la_fire(0x7fffffff);  // (the communication stream: issued now, before the gradients' collectives queue there)
 				la_fire(0);
@@ -1908,7 +1890,7 @@ struct NeusTestbed {
 			// gl.offset[valid + 1] on holds 0 after the backward, on every rank), so only the MLP blocks, the active levels'
 			// tables and the variance move. Overlapped: the gradients went out during the backward (net_backward).
 			const size_t grid_act = 2 * (size_t)gl.offset[std::min(valid + 1, gl.n_levels)];
-			if (xt) HIP_CHECK(hipEventRecord(xt[1], s));  // the backward is done (and the loss sums, when logged)
+			if (xt) HIP_CHECK(hipEventRecord(xt[1].get(), s));  // the backward is done (and the loss sums, when logged)
 			hipStream_t xs = xo ? x_stream() : stream;
 			coll_begin();
 			if (!xo) {
@@ -1919,16 +1901,16 @@ struct NeusTestbed {
 			if (get_loss) { allreduce_f32(loss_sum.p, 3, false, xs); allreduce_u32(health_buf.p, 2, xs); }
 			coll_end();
 			if (a_over) adam_issue(asp, lay.P, grads.p, false);  // the optimizer's last piece, behind the exchange
-			if (xt) HIP_CHECK(hipEventRecord(xt[2], xs));
+			if (xt) HIP_CHECK(hipEventRecord(xt[2].get(), xs));
 			x_join();
 		}
 		if (get_loss) {
 			if (loss_pending) consume_loss();  // (consumed at this step's start already; a restored state may leave one)
-			HIP_CHECK(hipMemcpyAsync(pinned, loss_sum.p, 3 * 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(hipMemcpyAsync(pinned + 52, health_buf.p, 8, hipMemcpyDeviceToHost, s));
-			if (!counters_done) HIP_CHECK(hipMemcpyAsync(pinned + 64, st.p, sizeof(StepState), hipMemcpyDeviceToHost, s));
-			HIP_CHECK(hipMemcpyAsync(pinned + 48, scan_tmp.p + offsetof(ScanState, fail), 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(hipEventRecord(ev_loss, s));
+			HIP_CHECK(hipMemcpyAsync(pinned.get(), loss_sum.p, 3 * 4, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(hipMemcpyAsync(pinned.get() + 52, health_buf.p, 8, hipMemcpyDeviceToHost, s));
+			if (!counters_done) HIP_CHECK(hipMemcpyAsync(pinned.get() + 64, st.p, sizeof(StepState), hipMemcpyDeviceToHost, s));
+			HIP_CHECK(hipMemcpyAsync(pinned.get() + 48, scan_tmp.p + offsetof(ScanState, fail), 4, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(hipEventRecord(ev_loss.get(), s));
 			loss_pending = true;
 		}
 		// the step-end counters ride on the Adam launch when the canonical optimizer steps (k_step_counters otherwise)
@@ -1960,8 +1942,8 @@ struct NeusTestbed {
 		if (!cfg.predict_global_movement || cur_frame == 0) canonical_step = training_step;
 		else if (training_step >= gm_steps()) canonical_step = training_step - gm_steps();
 		if (profiling) {
-			HIP_CHECK(hipMemcpyAsync(&prof_st[prof_par], st.p, sizeof(StepState), hipMemcpyDeviceToHost, stream));
-			HIP_CHECK(hipEventRecord(ev_done[prof_par], stream));
+			HIP_CHECK(hipMemcpyAsync(&prof_st.get()[prof_par], st.p, sizeof(StepState), hipMemcpyDeviceToHost, stream));
+			HIP_CHECK(hipEventRecord(ev_done[prof_par].get(), stream));
 			prof_pending[prof_par] = true;
 			prof_par ^= 1;
 			if (prof_pending[prof_par]) accumulate_phases(prof_par);  // the previous step
@@ -1999,13 +1981,13 @@ struct NeusTestbed {
 	}
 
 	void accumulate_phases(int par) {
-		HIP_CHECK(hipEventSynchronize(ev_done[par]));
+		HIP_CHECK(hipEventSynchronize(ev_done[par].get()));
 		for (int i = 0; i < N_PHASES; ++i) {
 			float ms = 0.f;
-			HIP_CHECK(hipEventElapsedTime(&ms, ev[par][i], ev[par][i + 1]));
+			HIP_CHECK(hipEventElapsedTime(&ms, ev[par][i].get(), ev[par][i + 1].get()));
 			phase_ms[i] += ms;
 		}
-		const StepState& h = prof_st[par];
+		const StepState& h = prof_st.get()[par];
 		phase_npre += h.n_kept;
 		phase_ntrain += std::min(h.compacted_global / std::max(1u, world), batch);
 		++phase_steps;
@@ -2020,23 +2002,24 @@ struct NeusTestbed {
 	// raise = false (stats): record the health bits and the abort without throwing
 	void consume_loss(bool raise = true) {
 		if (!loss_pending) return;
-		HIP_CHECK(hipEventSynchronize(ev_loss));
-		const StepState* sst = (const StepState*)(pinned + 64);
+		HIP_CHECK(hipEventSynchronize(ev_loss.get()));
+		const float* const pin = pinned.get();  // (the readback copies are complete)
+		const StepState* sst = (const StepState*)(pin + 64);
 		const float measured = (float)sst->compacted_global / (float)world;
 		const float scale = measured / (float)batch;
-		last_loss = pinned[0] * scale;
-		ek_loss = pinned[1] * scale;
-		mask_loss = pinned[2] * scale;
+		last_loss = pin[0] * scale;
+		ek_loss = pin[1] * scale;
+		mask_loss = pin[2] * scale;
 		last_rays_with_samples = sst->rays_ws_global;
 		last_keep_ratio = sst->n_kept ? measured / (float)sst->n_kept : 1.f;  // composited / kept (progressive inference)
 		choose_chunk_ends(sst->compacted_global, sst->rays_ws_global);
-		ray_loss = sst->rays_ws_global ? pinned[0] * (float)(sst->rays_per_batch * world) / (float)sst->rays_ws_global : 0.f;
+		ray_loss = sst->rays_ws_global ? pin[0] * (float)(sst->rays_per_batch * world) / (float)sst->rays_ws_global : 0.f;
 		if (!loss_ema_init) { loss_scalar_ema = last_loss; loss_ema_init = true; }
 		else loss_scalar_ema = 0.99f * loss_scalar_ema + 0.01f * last_loss;
 		// health: a non-finite loss sum (a NaN / Inf flag on the loss; the sums are all-reduced, so every
 		// rank raises it on the same step), and the zero-sample guard (testbed_nerf.cu:3542-3548: loss scalars 0,
 		// training stops - the Python frame() loop reads training_aborted)
-		if (!std::isfinite(pinned[0]) || !std::isfinite(pinned[1]) || !std::isfinite(pinned[2])) { nonfinite = true; aborted = true; }
+		if (!std::isfinite(pin[0]) || !std::isfinite(pin[1]) || !std::isfinite(pin[2])) { nonfinite = true; aborted = true; }
 		if (sst->compacted_global == 0) {
 			loss_scalar_ema = last_loss = ek_loss = mask_loss = 0.f;
 			aborted = true;
@@ -2045,8 +2028,8 @@ struct NeusTestbed {
 		// device health (sticky): a march that met a non-finite / negative t, a look-back scan that gave up waiting. Either
 		// means corrupted sampling or compaction bases: training stops with an error instead of continuing on bad data.
 		uint32_t scan_fail = 0, all[2] = {0, 0};
-		std::memcpy(&scan_fail, pinned + 48, 4);
-		std::memcpy(all, pinned + 52, 8);  // the health words summed over the ranks (this rank's alone at world 1)
+		std::memcpy(&scan_fail, pin + 48, 4);
+		std::memcpy(all, pin + 52, 8);  // the health words summed over the ranks (this rank's alone at world 1)
 		const uint32_t local = sst->fail_flags | (scan_fail ? STEP_FAIL_SCAN : 0u);
 		// the words are sums over the ranks, not bit sets: word 0 sums the ranks' fail_flags (the march sets only
 		// STEP_FAIL_MARCH_T there), word 1 the scans' give-up counters; any nonzero sum names its cause
@@ -2136,7 +2119,7 @@ int neus_testbed_train(NeusTestbed* tb, uint32_t n_steps) {
 		// the pattern alternates with its complement from step to step
 		struct FillScope { ~FillScope() { g_dbg_lds_fill = 0; g_dbg_xcd_shift = 0; } } fill_scope;
 		// (a lookahead left pending by a step that threw is dropped: the next step marches again, the same samples)
-		struct LaScope { NeusTestbed* t; ~LaScope() { if (t->la_pending) { (void)hipStreamSynchronize(t->la_stream); t->la_pending = false; } t->la_next_in_call = false; if (t->opt.la_stat) t->la_stat_report(); } } la_scope{tb};
+		struct LaScope { NeusTestbed* t; ~LaScope() { if (t->la_pending) { (void)hipStreamSynchronize(t->la_stream.get()); t->la_pending = false; } t->la_next_in_call = false; if (t->opt.la_stat) t->la_stat_report(); } } la_scope{tb};
 		for (uint32_t i = 0; i < n_steps; ++i) {
 			g_dbg_lds_fill = tb->dbg_lds_fill_all ? ((tb->training_step & 1) ? ~tb->dbg_lds_fill_all : tb->dbg_lds_fill_all) : 0u;
 			g_dbg_xcd_shift = tb->dbg_xcd_shift;
@@ -2556,11 +2539,11 @@ static void time_kernel_impl(NeusTestbed* tb, int kernel, int variant, int iters
 		}
 		// one event between consecutive launches (fence-free: timing only); the median launch is reported
 		iters = std::max(1, iters);
-		std::vector<hipEvent_t> evs((size_t)iters + 1);
-		for (auto& e : evs) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
+		std::vector<Event> evs((size_t)iters + 1);
+		for (auto& e : evs) e = make_event(hipEventDisableSystemFence);
 		for (int k = 0; k < iters; ++k) {
 			// (variant 98: no event between the launches - back to back, for the queue gaps of a kernel trace)
-			if (variant != 98 || k == 0) HIP_CHECK(hipEventRecord(evs[k], s));
+			if (variant != 98 || k == 0) HIP_CHECK(hipEventRecord(evs[k].get(), s));
 			switch (kernel) {
 			case 0: launch_march_count(s, MAX_RAYS, t.max_samples, t.st.p, dp, t.ds, t.bitfield.p, lin, t.rng.state, t.rng.inc, t.rays.p, t.startt.p, t.nreq.p, t.mwork,
 			                   nullptr, 0, t.opt.ray_cull ? t.occ_bbox.p : nullptr); break;
@@ -2627,18 +2610,17 @@ static void time_kernel_impl(NeusTestbed* tb, int kernel, int variant, int iters
 			default: throw std::runtime_error("unknown kernel id");
 			}
 		}
-		HIP_CHECK(hipEventRecord(evs[iters], s));
+		HIP_CHECK(hipEventRecord(evs[iters].get(), s));
 		HIP_CHECK(hipStreamSynchronize(s));
 		std::vector<float> d((size_t)iters);
 		if (variant == 98) {
 			float all = 0.f;
-			HIP_CHECK(hipEventElapsedTime(&all, evs[0], evs[iters]));
+			HIP_CHECK(hipEventElapsedTime(&all, evs[0].get(), evs[iters].get()));
 			for (auto& x : d) x = all / (float)iters;
 		} else
-			for (int k = 0; k < iters; ++k) HIP_CHECK(hipEventElapsedTime(&d[k], evs[k], evs[k + 1]));
+			for (int k = 0; k < iters; ++k) HIP_CHECK(hipEventElapsedTime(&d[k], evs[k].get(), evs[k + 1].get()));
 		std::sort(d.begin(), d.end());
 		*ms_out = d[(size_t)iters / 2];
-		for (auto& e : evs) HIP_CHECK(hipEventDestroy(e));
 	}
 }
 int neus_debug_march_stats(NeusTestbed* tb, uint32_t n, uint32_t* out) {
@@ -2831,7 +2813,9 @@ int neus_testbed_init_data_parallel_ex(NeusTestbed* tb, int rank, int world, con
 			if (!uid) throw std::runtime_error("init_data_parallel: no unique id");
 			ncclUniqueId id;
 			std::memcpy(&id, uid, 128);
-			NCCL_CHECK(ncclCommInitRank(&tb->comm, world, id, rank));
+			ncclComm_t c = nullptr;
+			NCCL_CHECK(ncclCommInitRank(&c, world, id, rank));
+			tb->comm.reset(c);
 		}
 	});
 }
@@ -3009,10 +2993,8 @@ int neus_debug_denorm_probe(int device, uint32_t n, uint32_t launches, uint64_t*
 	return guard([&] {
 		if (!stats || n == 0) throw std::runtime_error("neus_debug_denorm_probe: bad argument");
 		HIP_CHECK(hipSetDevice(device));
-		hipStream_t s = nullptr;
-		HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-		try { debug_denorm_probe(s, n, launches, stats); } catch (...) { (void)hipStreamDestroy(s); throw; }
-		HIP_CHECK(hipStreamDestroy(s));
+		const Stream s = make_stream(hipStreamNonBlocking);
+		debug_denorm_probe(s.get(), n, launches, stats);
 	});
 }
 // Development: raw bytes of one step-workspace buffer (ids: 0 sa, 1 ekt, 2 ck4, 3 cke, 4 racc, 5 rgr, 6 rT, 7 rek,
