@@ -395,7 +395,12 @@ int neus_debug_get_batch(NeusTestbed* tb, float* coords_out, uint16_t* dl_dout_o
  * stream of its own, every value compared with the CPU's bits. stats[10]: launches, mismatches, mismatches by 16-lane row
  * of the wave (4), values flushed to zero, distinct MODE register values (1 or 2), the first MODE, a differing MODE. */
 int neus_debug_denorm_probe(int device, uint32_t n, uint32_t launches, uint64_t* stats);
-/* Development: nbytes at offset of one step-workspace buffer (ids in testbed.cpp neus_debug_get_buffer). */
+/* Development: nbytes at offset of one step-workspace buffer (ids 0-15 and 20-34 in testbed.cpp neus_debug_get_buffer).
+ * What the occupancy update and the bitfield rebuild produce beside the grid and the bitfield:
+ *   40  bf_lin       the march's linear mip-0 words, 128*128*4 u32: word w holds cells (w >> 9, (w >> 2) & 127, 32 * (w & 3) + bit)
+ *   41  occ_bbox     6 f32: lo xyz, hi xyz of the occupied cells of every mip plus the pad (+-FLT_MAX for an empty field)
+ *   42  grid_mean    1 f32: the mean of cascade 0's cells, negative cells counted as 0
+ *   43  density_tmp  128^3 f32: the last update's splat target, before the EMA */
 int neus_debug_get_buffer(NeusTestbed* tb, int id, uint64_t offset, uint64_t nbytes, void* host);
 /* Development: the loss-gradient kernel replayed on the last step's state into a separate buffer (batch x 16 fp16). */
 int neus_debug_replay_loss_grad(NeusTestbed* tb, uint16_t* dl_dout_out);

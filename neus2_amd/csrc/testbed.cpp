@@ -2998,7 +2998,8 @@ int neus_debug_denorm_probe(int device, uint32_t n, uint32_t launches, uint64_t*
 	});
 }
 // Development: raw bytes of one step-workspace buffer (ids: 0 sa, 1 ekt, 2 ck4, 3 cke, 4 racc, 5 rgr, 6 rT, 7 rek,
-// 8 ccount, 9 net_out, 10 coords, 11 base, 12 numsteps, 13 cmap, 14 nreq)
+// 8 ccount, 9 net_out, 10 coords, 11 base, 12 numsteps, 13 cmap, 14 nreq; the occupancy update's products: 40 bf_lin,
+// 41 occ_bbox, 42 grid_mean, 43 density_tmp)
 int neus_debug_get_buffer(NeusTestbed* tb, int id, uint64_t offset, uint64_t nbytes, void* host) {
 	return guard([&] {
 		if (!tb->have_net) throw std::runtime_error("no network");
@@ -3024,6 +3025,10 @@ int neus_debug_get_buffer(NeusTestbed* tb, int id, uint64_t offset, uint64_t nby
 		case 15: pick(tb->dbg_dl.p, tb->dbg_dl.n * 2); break;
 		case 20: case 21: case 22: case 23: case 24: case 25: case 26: case 27: case 28: case 29: case 30: case 31: case 32: case 33: case 34:
 			pick(tb->dbg_snap[id - 20].p, tb->dbg_snap[id - 20].n); break;
+		case 40: pick(tb->bf_lin.p, (size_t)LIN_WORDS * 4); break;
+		case 41: pick(tb->occ_bbox.p, 6 * 4); break;
+		case 42: pick(tb->grid_mean.p, 4); break;
+		case 43: pick(tb->density_tmp.p, (size_t)GRID3 * 4); break;
 		default: throw std::runtime_error("debug_get_buffer: unknown id");
 		}
 		if (offset + nbytes > cap) throw std::runtime_error("debug_get_buffer: range past the buffer");

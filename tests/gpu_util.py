@@ -66,6 +66,20 @@ def env(**kv):
                 os.environ[k] = v
 
 
+OCC_BUFFERS = {"lin": (40, np.uint32, 128 ** 3 // 32), "bbox": (41, np.float32, 6), "mean": (42, np.float32, 1),
+               "density_tmp": (43, np.float32, 128 ** 3)}
+
+
+def occ_buffer(tb, name):
+    """One product of the occupancy update / bitfield rebuild through neus_debug_get_buffer: "lin" (the march's words of
+    the testbed's own field), "bbox", "mean" or "density_tmp"."""
+    from neus2_amd._lib import check, lib
+    bid, dtype, n = OCC_BUFFERS[name]
+    a = np.zeros(n, dtype)
+    check(lib().neus_debug_get_buffer(tb.handle, C.c_int(bid), C.c_uint64(0), C.c_uint64(a.nbytes), C.c_void_p(a.ctypes.data)))
+    return a
+
+
 def scatter_testbed(sc, mode, batch):
     """A base.json testbed on scene sc in one of the grid-gradient scatter modes: "regions" (per-block record regions,
     512-sample workgroups: the default), "regions1024" (1024-sample ones), "seg" (wide-block binning, 512), "seg1024" or
