@@ -369,6 +369,16 @@ int neus_debug_mlp_train(NeusTestbed* tb, void* hip_stream, uint32_t n, const fl
  * of n u32 on `hip_stream`, `reps` launches on one fresh state (the epoch re-arm), synchronous; failures = bounded-wait
  * give-ups (0 expected). */
 int neus_debug_exclusive_scan(void* hip_stream, const uint32_t* in, uint32_t* out, uint32_t n, int reps, uint32_t* failures);
+/* Development check of a progressive round's chunk scan (march.hip k_loss_scan_chunk): one launch of the given form
+ * (0: one lane per ray, 1: 16 lanes per ray) over the sample range [e0, e1) of the rays, on caller-provided device arrays,
+ * synchronous. numsteps: n_rays x {samples, first sample}; sa (float4) / ekt per sample; rays_in / n_rays_in (device) or
+ * null: the ray slots [0, n_rays) in order; ccount, racc (float4), rT, rek: the rays' state, read when e0 > 0 and written;
+ * ck4 (float4) / cke: the checkpoints, one per 8 samples; list / list_counter and rays_out / rays_out_counter (null: none):
+ * the next round's samples [e1, min(samples, e2)) of the rays still open, and those rays. */
+int neus_debug_loss_scan_chunk(void* hip_stream, int form, uint32_t n_rays, const uint32_t* numsteps, const float* sa, const float* ekt,
+                               uint32_t e0, uint32_t e1, uint32_t e2, const uint32_t* rays_in, const uint32_t* n_rays_in, uint32_t* ccount,
+                               float* racc, float* rT, float* rek, float* ck4, float* cke, uint32_t* list, uint32_t* list_counter,
+                               uint32_t* rays_out, uint32_t* rays_out_counter);
 /* Test hook of the scan's bounded wait: the same scan with its first tile never run, so every later tile gives up
  * waiting (n > 4096 elements); failures = the give-ups counted (nonzero expected). */
 int neus_debug_scan_giveup(void* hip_stream, const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* failures);

@@ -416,10 +416,12 @@ void launch_scan_prog_cut(hipStream_t s, void* scan_temp, const uint32_t* ccount
                           uint32_t* eval0, uint32_t* abort_if_none = nullptr);
 void launch_prog_next(hipStream_t s, uint32_t cap_rays, const uint32_t* rays_in, const uint32_t* n_in, const uint32_t* numsteps, const uint32_t* cut,
                       uint32_t e1, uint32_t e2, uint32_t* list, uint32_t* list_counter, uint32_t* rays_out, uint32_t* n_out);
+// group: the 16-lanes-per-ray form (k_loss_scan_chunk_group) instead of one lane per ray; the same bits in every output,
+// the appended entries in another order across rays
 void launch_loss_scan_chunk(hipStream_t s, uint32_t cap_rays, const uint32_t* numsteps, const LossWork& w, uint32_t* ccount, uint32_t e0,
                             uint32_t e1, uint32_t e2, uint32_t* list /* nullptr in the last round */, uint32_t* next_counter,
                             const uint32_t* rays_in = nullptr, const uint32_t* n_rays_in = nullptr, uint32_t* rays_out = nullptr,
-                            uint32_t* n_rays_out = nullptr);
+                            uint32_t* n_rays_out = nullptr, bool group = false);
 void launch_srgb_lut(hipStream_t s, float* lut);
 void launch_loss_ray(hipStream_t s, uint32_t cap_rays, StepState* st, DPInfo dp, const DevDataset& ds, const LossParams& lp, uint32_t* numsteps,
                      const uint32_t* ccount, const uint32_t* cbase, const LossWork& w, float* loss, float* ek, float* mask);

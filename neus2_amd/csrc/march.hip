@@ -1395,6 +1395,146 @@ __global__ void __launch_bounds__(64) SCAN_OCC k_loss_scan_chunk(uint32_t cap_ra
 	}
 }
 
+// The same round with SCAN_G = 16 lanes to a ray (a DPP row), 16 rays to a 256-thread workgroup: the form for a round of
+// a few thousand rays with long chunks (a cut step), where one lane per ray leaves 50-130 waves on the machine, each
+// issuing the whole recurrence once per sample. Here a lane holds one sample of the ray's next 16. Only the chains that
+// are serial in the reference stay serial, each as 16 steps of "take the left neighbour's value (the group's first lane:
+// the carried state), apply this lane's sample": T = T * (1 - alpha) first, then - with w = alpha * T and the three
+// w * c pointwise - the five sums r0, r1, r2, ws, ek side by side. A step recomputes the lanes that already hold their
+// final value from the same operands, so after step k lanes 0..k are exact and the rest are not read. The chains run
+// unconditionally over the slice; the stop (the first sample at the chunk end or with T < 1e-4 before it, a NaN T not
+// below it) is found from all 16 T at once, and the carried state is the chains' value at the last live sample: the
+// samples before the stop see exactly the operations, in the order, of the one-lane loop, so the bits are its bits. A
+// checkpoint is the chains' value before a live sample (the lane's own registers). Loads are clamped to the round's
+// [g0, gl] as in the other form, four slices in flight per lane (5 registers each). The appends are one reservation per
+// counter and workgroup; each ray's chunk is written by the whole workgroup.
+constexpr uint32_t SCAN_G = 16;
+__device__ __forceinline__ float row_prev(float carry, float x) { return dpp_f32<DPP_ROW_SHR + 1>(carry, x); }
+__device__ __forceinline__ float row_prev0(float x) {  // the group's first lane: 0
+	return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), DPP_ROW_SHR + 1, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float lane_get(float x, uint32_t src_lane) {
+	return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((int)(src_lane << 2), __builtin_bit_cast(int, x)));
+}
+__global__ void __launch_bounds__(256) k_loss_scan_chunk_group(uint32_t cap_rays, const uint32_t* __restrict__ numsteps, const float4* __restrict__ sa,
+                                                               const float* __restrict__ ekt, float4* __restrict__ ck4, float* __restrict__ cke,
+                                                               uint32_t* __restrict__ ccount, float4* __restrict__ racc, float* __restrict__ rT,
+                                                               float* __restrict__ rek, uint32_t e0, uint32_t e1, uint32_t e2,
+                                                               uint32_t* __restrict__ list, uint32_t* __restrict__ next_counter,
+                                                               const uint32_t* __restrict__ rays_in, const uint32_t* __restrict__ n_rays_in,
+                                                               uint32_t* __restrict__ rays_out, uint32_t* __restrict__ n_rays_out) {
+	constexpr uint32_t G = SCAN_G, RPB = 256 / G, NB = 4;
+	static_assert(G == 16, "a ray's lanes are one DPP row");
+	typedef float f4v __attribute__((ext_vector_type(4)));
+	__shared__ uint32_t s_app[3 * RPB + 2];  // per ray: next chunk's length, its first sample, the ray; the two reservations
+	const uint32_t tid = threadIdx.x, row = tid / G, el = tid % G, row0 = tid & 48u;  // row0: the group's first lane in its wave
+	const char* sab = (const char*)sa;
+	const char* ekb = (const char*)ekt;
+	const uint32_t n_slots = rays_in ? min(*n_rays_in, cap_rays) : cap_rays;
+	for (uint32_t w0 = blockIdx.x * RPB; w0 < n_slots; w0 += gridDim.x * RPB) {
+		const bool inr = w0 + row < n_slots;
+		const uint32_t i = rays_in ? (inr ? rays_in[w0 + row] : 0u) : w0 + row;
+		const uint32_t ns = inr ? numsteps[2 * i] : 0u, base = inr ? numsteps[2 * i + 1] : 0u;
+		RayScan S{1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0u};
+		bool open = inr && (e0 == 0 || ns > 0);  // this round runs (and stores) the ray's state
+		if (e0 > 0 && inr) {
+			const uint32_t cn = ccount[i];
+			const float T = rT[i];
+			const float4 a = racc[i];
+			const float ek = rek[i];
+			S.cn = cn;
+			if (!open || cn != e0 || e0 >= ns || T < 1e-4f) open = false;  // closed in an earlier round (or no samples)
+			else { S.T = T; S.r0 = a.x; S.r1 = a.y; S.r2 = a.z; S.ws = a.w; S.ek = ek; }
+		}
+		const uint32_t to = min(ns, e1);
+		bool live = open && to > e0;
+		const uint32_t g0 = live ? base + e0 : 0u, gl = live ? base + to - 1u : 0u;  // the round's samples [g0, gl]
+		auto fetch = [&](f4v& q, float& e, uint32_t c) {
+			const uint32_t g = min(g0 + c + el, gl);
+			q = *(const f4v*)(sab + ((size_t)g << 4));
+			e = *(const float*)(ekb + ((size_t)g << 2));
+		};
+		// the ray's samples [c, c + 16) of the round: one per lane
+		auto slice = [&](f4v& qs, float& es, uint32_t c) {
+			const f4v q = qs; const float e = es;
+			fetch(qs, es, c + NB * G);
+			const float f = 1.f - q[0];
+			float t = S.T, P = S.T;
+#pragma unroll
+			for (uint32_t u = 0; u < G; ++u) { t = row_prev(S.T, P); P = t * f; }  // t: T before the lane's sample, P: after it
+			const bool ok = (e0 + c + el < to) && !(t < 1e-4f);
+			const uint32_t stop = (uint32_t)(~__ballot(ok) >> row0) & 0xffffu;  // the group's samples at which the ray stops
+			const uint32_t nlive = live ? (stop ? (uint32_t)__ffs(stop) - 1u : G) : 0u;
+			const float w = q[0] * t;
+			const float p0 = w * q[1], p1 = w * q[2], p2 = w * q[3];
+			// the sums after the lane's sample. The group's first lane adds its carried sum to its term up front and takes
+			// 0 for its missing neighbour (the shift and the add are then one instruction): 0 + x is x but for x = -0, and
+			// carry + term is -0 only for a carry of -0, which a sum that started at +0 never is
+			const bool first = el == 0;
+			const float v0 = first ? S.r0 + p0 : p0, v1 = first ? S.r1 + p1 : p1, v2 = first ? S.r2 + p2 : p2;
+			const float vw = first ? S.ws + w : w, ve = first ? S.ek + e : e;
+			float a0 = v0, a1 = v1, a2 = v2, aw = vw, ae = ve;
+#pragma unroll
+			for (uint32_t u = 1; u < G; ++u) {
+				a0 = row_prev0(a0) + v0; a1 = row_prev0(a1) + v1; a2 = row_prev0(a2) + v2; aw = row_prev0(aw) + vw; ae = row_prev0(ae) + ve;
+			}
+			// and before it
+			const float b0 = row_prev(S.r0, a0), b1 = row_prev(S.r1, a1), b2 = row_prev(S.r2, a2), be = row_prev(S.ek, ae);
+			const uint32_t s = base + e0 + c + el;
+			if (el < nlive && (s & (SCAN_CK - 1)) == 0) { ck4[s / SCAN_CK] = make_float4(t, b0, b1, b2); cke[s / SCAN_CK] = be; }
+			// the state after the last live sample, from its lane (no live sample: the carried state stays)
+			const uint32_t src = row0 + (nlive ? nlive - 1u : 0u);
+			const float nT = lane_get(P, src), n0 = lane_get(a0, src), n1 = lane_get(a1, src), n2 = lane_get(a2, src);
+			const float nw = lane_get(aw, src), ne = lane_get(ae, src);
+			if (nlive) { S.T = nT; S.r0 = n0; S.r1 = n1; S.r2 = n2; S.ws = nw; S.ek = ne; }
+			S.cn += nlive;
+			live = nlive == G;
+		};
+		if (__ballot(live)) {
+			f4v qs[NB]; float es[NB];
+#pragma unroll
+			for (uint32_t bf = 0; bf < NB; ++bf) fetch(qs[bf], es[bf], bf * G);
+			for (uint32_t c = 0;; c += NB * G) {
+				bool more = true;
+#pragma unroll
+				for (uint32_t bf = 0; bf < NB; ++bf) {
+					if (more && __ballot(live && e0 + c + bf * G < to) == 0) more = false;
+					if (more) slice(qs[bf], es[bf], c + bf * G);
+				}
+				if (!more) break;
+			}
+		}
+		if (open && el == 0) {
+			ccount[i] = S.cn;
+			racc[i] = make_float4(S.r0, S.r1, S.r2, S.ws);
+			rT[i] = S.T;
+			rek[i] = S.ek;
+		}
+		if (list || rays_out) {
+			// the next round's chunk of every ray still open (no list: the open rays only), as in the other form
+			const uint32_t m = (open && S.cn == e1 && e1 < ns && S.T >= 1e-4f) ? min(ns, e2) - e1 : 0u;
+			__syncthreads();  // (the words' readers of the workgroup's previous rays)
+			if (el == 0) { s_app[row] = m; s_app[RPB + row] = base + e1; s_app[2 * RPB + row] = i; }
+			__syncthreads();
+			if (tid == 0) {
+				uint32_t total = 0, n_open = 0;
+				for (uint32_t r = 0; r < RPB; ++r) { total += s_app[r]; n_open += s_app[r] ? 1u : 0u; }
+				s_app[3 * RPB] = list && total ? atomicAdd(next_counter, total) : 0u;
+				s_app[3 * RPB + 1] = rays_out && total ? atomicAdd(n_rays_out, n_open) : 0u;
+			}
+			__syncthreads();
+			uint32_t p = s_app[3 * RPB], k = s_app[3 * RPB + 1];
+			for (uint32_t r = 0; r < RPB; ++r) {
+				const uint32_t m_r = s_app[r];
+				if (m_r == 0) continue;
+				if (list) { const uint32_t s_r = s_app[RPB + r]; for (uint32_t j = tid; j < m_r; j += 256) list[p + j] = s_r + j; }
+				if (rays_out && tid == r) rays_out[k] = s_app[2 * RPB + r];
+				p += m_r; ++k;
+			}
+		}
+	}
+}
+
 // ---- the compaction cut of the progressive rounds (fixed rays per batch; NeusTestbed::prog_cut)
 // The loss compacts the composited samples in ray-slot order and keeps the first `batch` (compute_loss_kernel_train_nerf,
 // testbed_nerf.cu:1682-1688: a ray whose compacted base is past the batch contributes nothing). After a round, ccount[i] is
@@ -1906,8 +2046,14 @@ void launch_loss_alpha_list(hipStream_t s, uint32_t cap_samples, const uint32_t*
 }
 void launch_loss_scan_chunk(hipStream_t s, uint32_t cap_rays, const uint32_t* numsteps, const LossWork& w, uint32_t* ccount, uint32_t e0,
                             uint32_t e1, uint32_t e2, uint32_t* list, uint32_t* next_counter, const uint32_t* rays_in, const uint32_t* n_rays_in,
-                            uint32_t* rays_out, uint32_t* n_rays_out) {
+                            uint32_t* rays_out, uint32_t* n_rays_out, bool group) {
 	dbg_lds_gate(s);
+	if (group) {
+		k_loss_scan_chunk_group<<<std::max<uint32_t>(1, std::min<uint32_t>((cap_rays + 15) / 16, 2048)), 256, 0, s>>>(
+			cap_rays, numsteps, w.sa, w.ekt, w.ck4, w.cke, ccount, w.racc, w.rT, w.rek, e0, e1, e2, list, next_counter, rays_in, n_rays_in,
+			rays_out, n_rays_out);
+		return;
+	}
 	k_loss_scan_chunk<<<std::max<uint32_t>(1, std::min<uint32_t>((cap_rays + 63) / 64, 8192)), 64, 0, s>>>(
 		cap_rays, numsteps, w.sa, w.ekt, w.ck4, w.cke, ccount, w.racc, w.rT, w.rek, e0, e1, e2, list, next_counter, rays_in, n_rays_in,
 		rays_out, n_rays_out);

@@ -91,6 +91,9 @@ struct NeusOptions {
 	// Two rounds, twice as long: steps 800 / 1600 0.815 / 0.895 -> 0.773 / 0.878 ms/step (profiles/r06y_chunk_ends_cut_sweep.txt)
 	float chunk_scale = 2.f;
 	int chunk_rounds = 2;
+	// NEUS_SCAN_FORM=lane / group: the progressive rounds' chunk scans one lane per ray (1) or 16 lanes per ray (2) on every step
+	// (bitwise A/B references; test_gpu_scan_chunk_forms.py); auto (0): 16 lanes per ray on the cut steps
+	uint32_t scan_form = 0;
 
 	// ---- occupancy update
 	// NEUS_OCC_SORT=0: the uniform samples in index order, not cell order (A/B reference)
@@ -143,6 +146,7 @@ struct NeusOptions {
 		o.chunk_ends = increasing_list("NEUS_CHUNK_ENDS");
 		o.chunk_scale = as_float("NEUS_CHUNK_SCALE", o.chunk_scale);
 		o.chunk_rounds = as_int("NEUS_CHUNK_ROUNDS", o.chunk_rounds);
+		o.scan_form = is("NEUS_SCAN_FORM", "lane") ? 1u : is("NEUS_SCAN_FORM", "group") ? 2u : 0u;
 		o.occ_sort = on_unless_0("NEUS_OCC_SORT");
 		o.occ_nu_sort = off_unless_1("NEUS_OCC_NU_SORT");
 		o.scatter_mode = is("NEUS_SCATTER", "binned") ? 1u : is("NEUS_SCATTER", "wide") ? 0u : 2u;

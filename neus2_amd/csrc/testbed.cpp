@@ -1685,6 +1685,9 @@ struct NeusTestbed {
 			// rounds of per-ray chunks, each: network on the round's samples, alpha, the recurrence continued (march.hip);
 			// the "infer" phase mark then covers the composite as well
 			uint32_t e0 = 0;
+			// the chunk scans' form (opt.scan_form): 16 lanes per ray on a cut step, whose rounds visit a few thousand
+			// rays with chunks of 64 samples and more; one lane per ray on every other step (many rays, short chunks)
+			const bool scan_group = opt.scan_form == 2 || (opt.scan_form == 0 && cut);
 			// the compaction cut (opt.prog_cut, cut_for): fixed rays per batch, not a step the host reads back (the loss readback
 			// steps, the last step of a train call), one rank's own batch
 			for (uint32_t k = 0; k < nch; ++k) {
@@ -1704,7 +1707,7 @@ struct NeusTestbed {
 				                       k ? open_rays[(k - 1) & 1].p : (sorted_rays ? rs_perm.p : nullptr),
 				                       k ? chunk_cnt.p + OPEN_CNT + k - 1 : (sorted_rays ? rsort.n_perm : nullptr),
 				                       more ? (cut_k ? open_raw.p : open_rays[k & 1].p) : nullptr,
-				                       more ? chunk_cnt.p + (cut_k ? RAW_CNT : OPEN_CNT) + k : nullptr);
+				                       more ? chunk_cnt.p + (cut_k ? RAW_CNT : OPEN_CNT) + k : nullptr, scan_group);
 				if (cut_k) {
 					// the cut after this round (cbase as the scan's scratch: the compaction rewrites it after the rounds), then
 					// the next round's rays and samples from the open rays at or before it
@@ -1719,7 +1722,7 @@ struct NeusTestbed {
 						launch_nerf_infer(s, lay.L, lay.W, cutw.p + CW_LENB_EFF, 0, c_in, gl, valid, params_h.p + lay.grid_off, mlp, net_out.p, 8192,
 						                  chunk_list.p + max_samples, &iab);
 						launch_loss_scan_chunk(s, MAX_RAYS, numsteps.p, w, ccount.p, 0, e1, e2, nullptr, nullptr, rs_perm.p + MAX_RAYS,
-						                       cutw.p + CW_NB_EFF, open_raw.p, chunk_cnt.p + RAW_CNT + k);
+						                       cutw.p + CW_NB_EFF, open_raw.p, chunk_cnt.p + RAW_CNT + k, scan_group);
 					}
 					launch_scan_prog_cut(s, scan_tmp.p, ccount.p, cbase.p, MAX_RAYS, batch, cutw.p, 1, split_b ? chunk_cnt.p : nullptr,
 					                     mcut ? cutw.p + CW_ABORT + (training_step & 1u) : nullptr);
@@ -2740,6 +2743,23 @@ int neus_debug_exclusive_scan(void* stream, const uint32_t* in, uint32_t* out, u
 		for (int r = 0; r < std::max(1, reps); ++r) launch_exclusive_scan(s, tmp.p, tb_, in, out, n);
 		HIP_CHECK(hipStreamSynchronize(s));
 		if (failures) *failures = scan_failures(tmp.p);
+	});
+}
+int neus_debug_loss_scan_chunk(void* stream, int form, uint32_t n_rays, const uint32_t* numsteps, const float* sa, const float* ekt, uint32_t e0,
+                               uint32_t e1, uint32_t e2, const uint32_t* rays_in, const uint32_t* n_rays_in, uint32_t* ccount, float* racc, float* rT,
+                               float* rek, float* ck4, float* cke, uint32_t* list, uint32_t* list_counter, uint32_t* rays_out,
+                               uint32_t* rays_out_counter) {
+	return guard([&] {
+		if (form != 0 && form != 1) throw std::runtime_error("neus_debug_loss_scan_chunk: form is 0 (lane) or 1 (group)");
+		if ((rays_in != nullptr) != (n_rays_in != nullptr) || (list && !list_counter) || (rays_out && !rays_out_counter))
+			throw std::runtime_error("neus_debug_loss_scan_chunk: a list without its counter");
+		hipStream_t s = (hipStream_t)stream;
+		LossWork w{};
+		w.sa = (float4*)sa; w.ekt = (float*)ekt; w.ck4 = (float4*)ck4; w.cke = cke; w.racc = (float4*)racc; w.rT = rT; w.rek = rek;
+		launch_loss_scan_chunk(s, n_rays, numsteps, w, ccount, e0, e1, e2, list, list_counter, rays_in, n_rays_in, rays_out, rays_out_counter,
+		                       form == 1);
+		HIP_CHECK(hipGetLastError());
+		HIP_CHECK(hipStreamSynchronize(s));
 	});
 }
 int neus_testbed_stream(NeusTestbed* tb, void** s) { return guard([&] { *s = (void*)tb->stream; }); }
