@@ -21,6 +21,8 @@
 // launcher's traffic: the default address is 127.0.0.1, and a non-loopback address exposes the port to its network.
 #pragma once
 
+#include "localgroup.h"  // neus::reduce_into: the one rank-order reduction of both groups
+
 #include <arpa/inet.h>
 #include <netinet/in.h>
 #include <netinet/tcp.h>
@@ -142,10 +144,6 @@ struct NeusHostGroup {
 			b += k; n -= (size_t)k;
 		}
 	}
-	template <class T> static void reduce(T* out, const T* v, size_t n, uint32_t op) {
-		if (op == SUM) for (size_t k = 0; k < n; ++k) out[k] = (T)(out[k] + v[k]);
-		else for (size_t k = 0; k < n; ++k) out[k] = out[k] < v[k] ? v[k] : out[k];
-	}
 	// In-place all-reduce of a host buffer (the host function's body). Rank order reduction on rank 0.
 	void allreduce_host(void* buf, size_t bytes, uint32_t type, uint32_t op) {
 		if (failed.load()) return;
@@ -170,8 +168,8 @@ struct NeusHostGroup {
 					                         std::to_string(a.bytes) + " B) than rank 0 (#" + std::to_string(h.seq) + ", " + std::to_string(h.bytes) +
 					                         " B): the ranks' step settings differ");
 				recv_all(fd[r], recv_buf.data(), bytes);
-				if (type == F32) reduce((float*)buf, (const float*)recv_buf.data(), bytes / 4, op);
-				else reduce((uint32_t*)buf, (const uint32_t*)recv_buf.data(), bytes / 4, op);
+				if (type == F32) neus::reduce_into((float*)buf, (const float*)recv_buf.data(), bytes / 4, op != SUM);
+				else neus::reduce_into((uint32_t*)buf, (const uint32_t*)recv_buf.data(), bytes / 4, op != SUM);
 			}
 			for (int r = 1; r < world; ++r) {
 				send_all(fd[r], &h, sizeof(h));

@@ -1,6 +1,8 @@
 // Host orchestration of the NeuS2 training hot path on gfx950 and the testbed part of the C-ABI (include/neus2_hip.h):
-// every entry point that takes a NeusTestbed, the groups and the debug hooks. The operator modules and the rendering
-// operators are in operators.cpp, which uses a testbed only through the functions of core.h, defined here.
+// every entry point that takes a NeusTestbed and the debug hooks. The operator modules and the rendering operators are
+// in operators.cpp, which uses a testbed only through the functions of core.h, defined here. The data-parallel exchange
+// (transports, exchange stream, all-reduces, the groups' entry points) is neus::Exchange, exchange.h: the step here
+// decides when and what is exchanged.
 //
 // NeusTestbed restates the training-relevant part of the reference Testbed
 // (include/neural-graphics-primitives/testbed.h:63-940; src/testbed.cu:2084-2349, 2640-2736;
@@ -13,25 +15,19 @@
 #include "kernels.h"
 #include "scan_lookback.h"
 #include "json_lite.h"
-#include "hostgroup.h"
 #include "options.h"
 #include "host_util.h"
+#include "exchange.h"
 #include "core.h"
 #include "../../include/neus2_hip.h"
-
-#include <rccl/rccl.h>
 
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <functional>
-#include <chrono>
 #include <cmath>
-#include <condition_variable>
-#include <mutex>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
 #include <random>
 #include <stdexcept>
 #include <string>
@@ -42,12 +38,6 @@ using namespace neus;
 namespace {
 
 thread_local std::string g_err;
-
-#define NCCL_CHECK(x)                                                                                  \
-	do {                                                                                               \
-		ncclResult_t r_ = (x);                                                                         \
-		if (r_ != ncclSuccess) throw std::runtime_error(std::string(#x) + " failed: " + ncclGetErrorString(r_)); \
-	} while (0)
 
 // Debug (options.h NeusAllocDebug): the fill / the listing of the fresh device allocations, numbered from the last
 // neus_testbed_create, where the pair is latched for the process
@@ -111,49 +101,6 @@ void ld_pixel_offset(uint32_t spp, float out[2]) {
 }
 
 } // namespace
-
-// In-process data-parallel group: `world` testbeds driven from `world` host threads exchange through host staging
-// buffers (sum in rank order, max), with the same call sequence as the RCCL path. It lets the data-parallel step
-// (sharded occupancy update, gradient / counter / loss / DeltaNetwork all-reduces) run with several ranks on one
-// device, e.g. in tests; production ranks use RCCL (neus_testbed_init_data_parallel).
-struct NeusLocalGroup {
-	enum Op { SUM, MAX };
-	uint32_t world;
-	std::mutex mu;
-	std::condition_variable cv;
-	uint32_t arrived = 0, generation = 0;
-	bool failed = false;  // a rank timed out: every later collective fails fast instead of pairing the wrong ranks
-	std::vector<std::vector<uint8_t>> stage;
-	explicit NeusLocalGroup(uint32_t w) : world(w), stage(w) {}
-	void barrier() {
-		std::unique_lock<std::mutex> lk(mu);
-		if (failed) throw std::runtime_error("local group: a previous collective failed (the group is poisoned)");
-		const uint32_t gen = generation;
-		if (++arrived == world) { arrived = 0; ++generation; cv.notify_all(); return; }
-		if (!cv.wait_for(lk, std::chrono::seconds(120), [&] { return generation != gen || failed; }) || failed) {
-			if (generation == gen) --arrived;  // this rank's arrival is withdrawn
-			failed = true;
-			cv.notify_all();
-			throw std::runtime_error("local group: barrier timeout (a rank did not reach the collective)");
-		}
-	}
-	// in-place all-reduce of n elements of T on the device, on `s` (host-synchronous)
-	template <class T> void allreduce(uint32_t rank, T* dev, size_t n, Op op, hipStream_t s) {
-		std::vector<uint8_t>& mine = stage[rank];
-		mine.resize(n * sizeof(T));
-		HIP_CHECK(hipMemcpyAsync(mine.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		barrier();
-		std::vector<T> out(n);
-		for (uint32_t r = 0; r < world; ++r) {
-			const T* v = (const T*)stage[r].data();
-			for (size_t k = 0; k < n; ++k) out[k] = r == 0 ? v[k] : (op == SUM ? (T)(out[k] + v[k]) : std::max(out[k], v[k]));
-		}
-		barrier();  // every rank has read every stage before the next collective overwrites one
-		HIP_CHECK(hipMemcpyAsync(dev, out.data(), n * sizeof(T), hipMemcpyHostToDevice, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-	}
-};
 
 struct NeusTestbed {
 	const NeusOptions opt = NeusOptions::from_env();  // the NEUS_* switches, read once: they hold for the testbed's life
@@ -435,50 +382,17 @@ struct NeusTestbed {
 	                          // give-up count; [64..]: StepState copy
 	bool loss_pending = false;
 	Event ev_loss;  // after the logged step's readback copies (consume_loss waits on it, not on the stream)
-	// data parallel: RCCL communicator (production) or an in-process group
-	Handle<ncclComm_t, ncclCommDestroy> comm;
-	NeusLocalGroup* group = nullptr;
-	// cross-process host-staged group (hostgroup.h): every collective staged on comm_stream through a pinned buffer
-	NeusHostGroup* hgroup = nullptr;
-	Pinned<uint8_t> hg_stage;
-	size_t hg_stage_bytes = 0;
-	uint32_t rank = 0, world = 1;
-	// the exchange setting must be the same on every rank (the overlapped and grouped exchanges issue different
-	// collective sequences): checked by an all-reduce at the first step after init or a change
-	bool overlap_verified = false;
-	bool force_coll = false;  // issue the collectives at world 1 too (a forced one-rank communicator, tests)
-	// Overlapped gradient exchange: each finished gradient range is all-reduced as soon as its producer
-	// finishes - the MLP blocks after the weight-gradient reduction, the grid levels group by group beside the scatter's
-	// accumulation of the later groups - on comm_stream (RCCL; one stream keeps every rank's collectives in one order),
-	// which the step's stream joins before the optimizer. Off (NEUS_EXCHANGE_OVERLAP=0, neus_testbed_set_exchange_overlap):
-	// one grouped exchange after the backward. Elementwise sums are the same either way (bitwise with two ranks).
-	bool exchange_overlap = opt.exchange_overlap;
-	Stream comm_stream;
-	Event ev_x[16];
-	uint32_t ev_x_n = 0;
-	Event ev_xdone;
-	bool x_pending = false;
+	// data parallel (exchange.h): the transport, this rank's place in it, the exchange stream, the all-reduces and their
+	// counters; bound to the current stream and the step's priority
+	Exchange x{stream, main_prio, opt.exchange_overlap};
+	DPInfo dp_info() const { return DPInfo{x.rank(), x.world()}; }
+	// One of the exchange's attaches (neus_testbed_init_*): the loss normalisation follows the world size the attach left,
+	// also when it threw after setting it
+	template <class F> void attach(F&& f) {
+		struct Renorm { NeusTestbed* t; ~Renorm() { t->tbuf.indeed_batch = (float)t->batch * (float)t->x.world(); } } renorm{this};
+		f();
+	}
 	static constexpr uint32_t X_GROUPS = 3;   // grid level groups of the overlapped exchange (~equal bytes at L=14)
-	// on comm_stream after the work queued so far on the step's stream (RCCL); the in-process group stages on the host
-	hipStream_t x_stream() {
-		if (!comm && !hgroup) return stream;
-		if (!comm_stream) {
-			comm_stream = main_prio ? make_stream(hipStreamNonBlocking, main_prio) : make_stream(hipStreamNonBlocking);
-			ev_xdone = make_event(hipEventDisableTiming);
-		}
-		Event& e = ev_x[ev_x_n++ % 16];
-		ensure_event(e, hipEventDisableTiming);
-		HIP_CHECK(hipEventRecord(e.get(), stream));
-		HIP_CHECK(hipStreamWaitEvent(comm_stream.get(), e.get(), 0));
-		x_pending = true;
-		return comm_stream.get();
-	}
-	void x_join() {  // the step's stream waits for every exchange issued on comm_stream
-		if (!x_pending) return;
-		HIP_CHECK(hipEventRecord(ev_xdone.get(), comm_stream.get()));
-		HIP_CHECK(hipStreamWaitEvent(stream, ev_xdone.get(), 0));
-		x_pending = false;
-	}
 	// level groups of the overlapped exchange: the active levels cut where the cumulative parameter count passes 1/3, 2/3
 	ScatterSplit x_split(uint32_t valid, float* grid_grads) {
 		ScatterSplit sp{};
@@ -491,13 +405,11 @@ struct NeusTestbed {
 		for (; gi + 1 < X_GROUPS; ++gi) sp.level_end[gi] = n_act;
 		sp.level_end[X_GROUPS - 1] = n_act;
 		sp.done = [this, grid_grads](uint32_t lo, uint32_t hi) {
-			hipStream_t xs = x_stream();
-			allreduce_f32(grid_grads + 2 * (size_t)gl.offset[lo], 2 * (size_t)(gl.offset[hi] - gl.offset[lo]), false, xs);
+			hipStream_t xs = x.gated();
+			x.allreduce_f32(grid_grads + 2 * (size_t)gl.offset[lo], 2 * (size_t)(gl.offset[hi] - gl.offset[lo]), false, xs);
 		};
 		return sp;
 	}
-	uint64_t coll_calls = 0, coll_bytes = 0, coll_bytes_step = 0;
-	bool coll_on() const { return world > 1 || force_coll; }
 	// profiling
 	bool profiling = false;
 	static constexpr int N_PHASES = NEUS_N_PHASES;
@@ -556,12 +468,12 @@ struct NeusTestbed {
 	~NeusTestbed() {
 		// every stream of the testbed idle before anything is released: no queued work then reads an event, a pinned block or
 		// a device buffer, so the members (Dev buffers included) may go in any order, before or after the streams
-		for (hipStream_t q : {stream_own.get(), aux_stream.get(), la_stream.get(), comm_stream.get()})
+		for (hipStream_t q : {stream_own.get(), aux_stream.get(), la_stream.get(), x.stream()})
 			if (q) (void)hipStreamSynchronize(q);
-		comm.reset();  // the communicator before any stream: it was issuing on the exchange stream or the step's
+		x.release_comm();  // the communicator before any stream: it was issuing on the exchange stream or the step's
 		// the streams in the order they have always gone back to the runtime (it is not neutral to that, see the
 		// constructor): by these explicit resets, declaration order would give comm, la, aux, step
-		aux_stream.reset(); la_stream.reset(); comm_stream.reset(); stream_own.reset();
+		aux_stream.reset(); la_stream.reset(); x.release_stream(); stream_own.reset();
 	}
 
 	// ------------------------------------------------------------ dataset (load_nerf, testbed_nerf.cu:2964-3095)
@@ -747,7 +659,7 @@ struct NeusTestbed {
 		wgrad_partial.alloc((size_t)mlp_blocks * l.n_matrix);
 		tbuf.wpartial = wgrad_partial.p;
 		tbuf.n_matrix = l.n_matrix; tbuf.off_d1 = l.off_d1; tbuf.off_r0 = l.off_r0; tbuf.off_r1 = l.off_r1; tbuf.off_r2 = l.off_r2;
-		tbuf.indeed_batch = (float)batch * (float)world;
+		tbuf.indeed_batch = (float)batch * (float)x.world();
 		// binned grid-gradient scatter workspace (grid.hip)
 		swork = ScatterWork{};
 		swork.n_blocks = (batch + 255) / 256;
@@ -1031,9 +943,9 @@ struct NeusTestbed {
 		launch_mlp_grad_reduce(s, grad_reduce(n, g, n_train_ptr));
 		la_fire(3);
 		if (exchange) {  // the MLP blocks and the variance are final: their exchange runs beside the grid scatter
-			hipStream_t xs = x_stream();
-			allreduce_f32(g, lay.grid_off, false, xs);
-			allreduce_f32(g + lay.var_off, lay.P - lay.var_off, false, xs);
+			hipStream_t xs = x.gated();
+			x.allreduce_f32(g, lay.grid_off, false, xs);
+			x.allreduce_f32(g + lay.var_off, lay.P - lay.var_off, false, xs);
 			if (as) as->on = xs;  // (the optimizer's pieces follow their ranges' all-reduces on the exchange stream)
 		}
 		if (as) adam_issue(*as, lay.grid_off, g, true);  // the MLP blocks (and their transposed copies) beside the scatter
@@ -1053,68 +965,8 @@ struct NeusTestbed {
 		                    scan_tmp_bytes, (exchange || a_split) && sw.mode == 2 ? &sp : nullptr);
 		if (exchange && sw.mode != 2) {  // other scatter modes: the grid exchange after the whole scatter
 			const size_t grid_act = 2 * (size_t)gl.offset[std::min(valid + 1, gl.n_levels)];
-			allreduce_f32(g + lay.grid_off, grid_act, false, x_stream());
+			x.allreduce_f32(g + lay.grid_off, grid_act, false, x.gated());
 		}
-	}
-
-	// ------------------------------------------------------------ collectives
-	void coll_begin() { if (comm) NCCL_CHECK(ncclGroupStart()); }
-	void coll_end() { if (comm) NCCL_CHECK(ncclGroupEnd()); }
-	void allreduce_f32(float* p, size_t n, bool max_op = false, hipStream_t on = nullptr) {
-		if (!coll_on() || n == 0) return;
-		++coll_calls; coll_bytes += n * 4; coll_bytes_step += n * 4;
-		if (comm) NCCL_CHECK(ncclAllReduce(p, p, n, ncclFloat32, max_op ? ncclMax : ncclSum, comm.get(), on ? on : stream));
-		else if (hgroup) hg_allreduce(p, n * 4, NeusHostGroup::F32, max_op ? NeusHostGroup::MAX : NeusHostGroup::SUM, on);
-		else if (group) group->allreduce<float>(rank, p, n, max_op ? NeusLocalGroup::MAX : NeusLocalGroup::SUM, stream);
-		else throw std::runtime_error("data parallel: no communicator");
-	}
-	void allreduce_u32(uint32_t* p, size_t n, hipStream_t on = nullptr) {
-		if (!coll_on() || n == 0) return;
-		++coll_calls; coll_bytes += n * 4; coll_bytes_step += n * 4;
-		if (comm) NCCL_CHECK(ncclAllReduce(p, p, n, ncclUint32, ncclSum, comm.get(), on ? on : stream));
-		else if (hgroup) hg_allreduce(p, n * 4, NeusHostGroup::U32, NeusHostGroup::SUM, on);
-		else if (group) group->allreduce<uint32_t>(rank, p, n, NeusLocalGroup::SUM, stream);
-		else throw std::runtime_error("data parallel: no communicator");
-	}
-	// A host-group collective on comm_stream: device -> pinned stage, the socket exchange in a host function, stage ->
-	// device. Issued from the step's stream (on == nullptr / stream), it is gated after the work queued there and the step's
-	// stream waits for it; issued on comm_stream (the overlapped exchange), the stream order is the gate.
-	void hg_allreduce(void* dev, size_t bytes, uint32_t type, uint32_t op, hipStream_t on) {
-		const bool own = !(on && on == comm_stream.get());
-		hipStream_t cs = own ? x_stream() : on;
-		if (bytes > hg_stage_bytes) {  // grow: the queued collectives still read the old stage
-			if (comm_stream) HIP_CHECK(hipStreamSynchronize(comm_stream.get()));
-			hg_stage.reset();  // (freed before the larger one is allocated)
-			hg_stage_bytes = 0;
-			hg_stage = make_pinned<uint8_t>(std::max(bytes, (size_t)1 << 20));
-			hg_stage_bytes = std::max(bytes, (size_t)1 << 20);
-		}
-		HIP_CHECK(hipMemcpyAsync(hg_stage.get(), dev, bytes, hipMemcpyDeviceToHost, cs));
-		auto c = std::make_unique<HostCollCall>(HostCollCall{hgroup, hg_stage.get(), bytes, type, op});
-		HIP_CHECK(hipLaunchHostFunc(cs, [](void* a) {
-			std::unique_ptr<HostCollCall> c((HostCollCall*)a);
-			c->g->allreduce_host(c->host, c->bytes, c->type, c->op);
-		}, c.get()));
-		(void)c.release();  // the queued host function owns it from here
-		HIP_CHECK(hipMemcpyAsync(dev, hg_stage.get(), bytes, hipMemcpyHostToDevice, cs));
-		if (own) x_join();
-	}
-	// every rank must run the same exchange (overlapped or grouped): sum of the setting over the ranks is 0 or world
-	void verify_uniform_exchange() {
-		if (overlap_verified || !coll_on()) return;
-		health_buf.alloc(4);
-		const uint32_t v[2] = {exchange_overlap ? 1u : 0u, 1u};
-		HIP_CHECK(hipMemcpyAsync(health_buf.p + 2, v, 8, hipMemcpyHostToDevice, stream));
-		allreduce_u32(health_buf.p + 2, 2);
-		uint32_t h[2] = {0, 0};
-		HIP_CHECK(hipMemcpyAsync(h, health_buf.p + 2, 8, hipMemcpyDeviceToHost, stream));
-		HIP_CHECK(hipStreamSynchronize(stream));
-		if (hgroup) hgroup->check();
-		if (h[1] != world) throw std::runtime_error("data parallel: the exchange-setting check saw " + std::to_string(h[1]) + " of " + std::to_string(world) + " ranks");
-		if (h[0] != 0 && h[0] != world)
-			throw std::runtime_error("data parallel: the exchange overlap is on for " + std::to_string(h[0]) + " of " + std::to_string(world) +
-			                         " ranks (neus_testbed_set_exchange_overlap / NEUS_EXCHANGE_OVERLAP must be the same on every rank)");
-		overlap_verified = true;
 	}
 
 	// ------------------------------------------------------------ occupancy grid (testbed_nerf.cu:3293-3397, 4003-4016)
@@ -1125,6 +977,7 @@ struct NeusTestbed {
 		// the first 256 steps' all-cells uniform pass writes every cell exactly once (fused path, one cascade): on a
 		// single GPU no clearing is needed; with shards each rank writes only its cells, the rest must read 0
 		const bool exclusive = !use_delta && n_nonuniform == 0 && n_uniform == GRID3 && max_cascade == 0;
+		const uint32_t rank = x.rank(), world = x.world();
 		if (!exclusive || world > 1) HIP_CHECK(hipMemsetAsync(density_tmp.p, 0, n_cells * 4, s));
 		// data parallel: rank r evaluates the global samples [lo, hi) (same density_grid_rng on every rank; in the
 		// exclusive pass the cells [lo, hi), i.e. the samples that land there); the max-splatted grids are then
@@ -1176,7 +1029,7 @@ struct NeusTestbed {
 			launch_nerf_density(s, lay.L, lay.W, N, occ_pos.p, gl, valid, params_h.p + lay.grid_off, mlp, occ_density.p);
 			launch_splat_max(s, N, occ_idx.p, occ_density.p, density_tmp.p);
 		}
-		allreduce_f32(density_tmp.p, n_cells, true);
+		x.allreduce_f32(density_tmp.p, n_cells, true);
 		// EMA + mean partials (one launch), final mean, bitfield, mip pools + the march's linear words (one launch)
 		launch_ema_mean(s, n_cells, cfg.density_grid_decay, density_grid.p, density_tmp.p, grid_partial.p, grid_mean.p);
 		++density_grid_ema_step;
@@ -1249,7 +1102,7 @@ struct NeusTestbed {
 	}
 	void adam_join(AdamSplit& a, const float* g) {
 		adam_issue(a, lay.P, g, false);  // (whatever is left: the levels past the valid one, the variance)
-		if (!a.on) {  // (on the exchange stream the step's x_join has waited for every piece already)
+		if (!a.on) {  // (on the exchange stream the step's join has waited for every piece already)
 			HIP_CHECK(hipEventRecord(ad_done.get(), ad_stream));
 			HIP_CHECK(hipStreamWaitEvent(stream, ad_done.get(), 0));
 		}
@@ -1343,39 +1196,6 @@ struct NeusTestbed {
 		++it_steps;
 		it_n = 0;
 	}
-
-	// Exchange timing (neus_testbed_set_exchange_timing, data parallel): per step, an event on the step's stream where the
-	// backward is done (the gradients' last use before the join) and one on the exchange's stream after its last
-	// collective. exposed = max(0, done - backward done): what the join before Adam waits for; span = done - the loss's end
-	// (the counters' exchange starts there). A ring of event sets collected lazily (the oldest has long completed when the
-	// ring wraps, the host running at most 16 steps ahead), so timing runs inside timed regions without a per-step sync.
-	bool xt_on = false;
-	static constexpr int XT_RING = 64;
-	Event xt_ev[XT_RING][3];  // [loss end (step stream), backward done (step stream), exchange done (exchange stream)]
-	int xt_head = 0, xt_n = 0;
-	double xt_exposed_ms = 0.0, xt_span_ms = 0.0;
-	uint64_t xt_steps = 0;
-	Event* xt_slot() {
-		if (xt_n == XT_RING) xt_collect_one();
-		Event* e = xt_ev[(xt_head + xt_n) % XT_RING];
-		for (int k = 0; k < 3; ++k) ensure_event(e[k]);
-		++xt_n;
-		return e;
-	}
-	void xt_collect_one() {
-		Event* e = xt_ev[xt_head];
-		HIP_CHECK(hipEventSynchronize(e[2].get()));
-		HIP_CHECK(hipEventSynchronize(e[1].get()));
-		float exposed = 0.f, span = 0.f;
-		HIP_CHECK(hipEventElapsedTime(&exposed, e[1].get(), e[2].get()));
-		HIP_CHECK(hipEventElapsedTime(&span, e[0].get(), e[2].get()));
-		xt_exposed_ms += std::max(0.f, exposed);
-		xt_span_ms += span;
-		++xt_steps;
-		xt_head = (xt_head + 1) % XT_RING;
-		--xt_n;
-	}
-	void xt_collect_all() { while (xt_n) xt_collect_one(); }
 
 	// ------------------------------------------------------------ rendering (render_to_cpu, python_api.cu:123-169)
 	// NerfTracer::init_rays_from_camera + trace (testbed_nerf.cu:2397-2600) once per spp, accumulated in linear
@@ -1561,7 +1381,7 @@ struct NeusTestbed {
 		}
 		if (!a) return;
 		// this testbed's streams drained (not the device's: another rank of an in-process group may share it)
-		for (hipStream_t q : {stream_own.get(), aux_stream.get(), la_stream.get(), comm_stream.get()})
+		for (hipStream_t q : {stream_own.get(), aux_stream.get(), la_stream.get(), x.stream()})
 			if (q) HIP_CHECK(hipStreamSynchronize(q));
 		la_pending = false;
 		la_deferred = nullptr;
@@ -1577,10 +1397,10 @@ struct NeusTestbed {
 			// the step before was cut too: its requested count in full (its rays again, from its rng and its n_rays_total), so
 			// that this step's cap is the reference's exactly (the bitfield is the one it marched: no occupancy update since)
 			StepState t = h;
-			t.n_rays_total = h.n_rays_total - h.rays_per_batch * world;
+			t.n_rays_total = h.n_rays_total - h.rays_per_batch * x.world();
 			st_recount.alloc(1);
 			HIP_CHECK(hipMemcpy(st_recount.p, &t, sizeof(t), hipMemcpyHostToDevice));
-			launch_march_count(stream, MAX_RAYS, max_samples, st_recount.p, DPInfo{rank, world}, ds, bitfield.p, bf_lin.p, s1.rng.state, s1.rng.inc,
+			launch_march_count(stream, MAX_RAYS, max_samples, st_recount.p, dp_info(), ds, bitfield.p, bf_lin.p, s1.rng.state, s1.rng.inc,
 			                   rays.p, startt.p, nreq.p, mwork, nullptr, 0, opt.ray_cull ? occ_bbox.p : nullptr);
 			launch_march_write(stream, MAX_RAYS, st_recount.p, ds, rays.p, mwork, nreq.p, base.p, numsteps.p, coords.p, nullptr, max_samples,
 			                   scan_tmp.p, nullptr, 0);
@@ -1609,8 +1429,8 @@ struct NeusTestbed {
 		snap[0] = StepSnap{training_step, canonical_step, adam_step, call_left, enc_step, lr_factor, rng, la_steps, cut_steps, adam_split_steps, mcut_steps};
 		mc_hist[1] = mc_hist[0];
 		mc_hist[0] = false;
-		if (hgroup) hgroup->check();
-		verify_uniform_exchange();
+		x.check();
+		if (x.unverified()) { health_buf.alloc(4); x.verify_uniform(health_buf.p + 2); }
 		// the readback of 16 steps back (long done on the device) is checked at this step boundary, before anything of
 		// this step is queued: a health failure (all-reduced, so every rank sees it) stops every rank on the same step
 		// with no collective half-issued and no step half-applied; the host stays at most 16 steps ahead of the device
@@ -1642,7 +1462,8 @@ struct NeusTestbed {
 		}
 		// ---- train_nerf_step (testbed_nerf.cu:3723-4001)
 		if (training_step == 0 || canonical_step == 0) HIP_CHECK(hipMemsetAsync(&st.p->n_rays_total, 0, 4, s));
-		const DPInfo dp{rank, world};  // (n_kept, n_rays_with_samples: zeroed by k_ray_gen)
+		const uint32_t world = x.world();
+		const DPInfo dp = dp_info();  // (n_kept, n_rays_with_samples: zeroed by k_ray_gen)
 		mark(1);
 		// progressive (cut-off-aware) inference this step: its round-0 list is written by the march
 		const bool progressive = progressive_mode == 2 || (progressive_mode == 1 && last_keep_ratio < PROGRESSIVE_RATIO);
@@ -1675,7 +1496,7 @@ struct NeusTestbed {
 		lp.loss_scale = LOSS_SCALE; lp.ek_w = cfg.ek_loss_weight; lp.mask_w = cfg.mask_loss_weight; lp.cos_anneal = cos_anneal();
 		lp.max_compacted = batch; lp.rng_state = rng.state; lp.rng_inc = rng.inc; lp.jt = jump_table();
 		lp.abort_w = cutw.p + CW_ABORT; lp.abort_slot = training_step & 1u;
-		if (risky && !coll_on()) {
+		if (risky && !x.on()) {
 			// one rank: the word goes straight from k_loss_grad to host memory (no copy, no event on the step's streams)
 			lp.abort_host = arm_abort_word();
 		}
@@ -1761,20 +1582,20 @@ struct NeusTestbed {
 		// right after the loss into StepState::compacted_global / rays_ws_global (compacted_counter stays this rank's
 		// training batch for the backward). On the communication stream with the overlapped exchange, so the backward
 		// does not wait for it; the gradients' collectives follow on the same stream, in the same order on every rank.
-		const bool xo = coll_on() && exchange_overlap && (!dyn || train_canonical);
-		coll_bytes_step = 0;
+		const bool xo = x.on() && x.overlap() && (!dyn || train_canonical);
+		x.reset_step_bytes();
 		hipStream_t cs = s;  // the stream the counters (and the lookahead's start) are ordered on
-		Event* xt = coll_on() && xt_on ? xt_slot() : nullptr;
+		Event* xt = x.timing_slot();
 		if (xt) HIP_CHECK(hipEventRecord(xt[0].get(), s));
-		if (coll_on()) {
-			cs = xo ? x_stream() : stream;
-			coll_begin();
-			allreduce_u32(&st.p->compacted_global, 3, cs);  // (+ cut_abort: every rank re-runs the step, or none)
-			coll_end();
+		if (x.on()) {
+			cs = xo ? x.gated() : stream;
+			x.begin();
+			x.allreduce_u32(&st.p->compacted_global, 3, cs);  // (+ cut_abort: every rank re-runs the step, or none)
+			x.end();
 		}
 		if (risky) {
 			abort_pending = true;
-			abort_direct = !coll_on();
+			abort_direct = !x.on();
 		}
 		// ---- lookahead: the next step's ray sampling beside this step's backward (opt.lookahead; see the members)
 		const bool get_loss = training_step % 16 == 0;
@@ -1788,7 +1609,7 @@ struct NeusTestbed {
 		// with a group, the all-reduced word goes to the host from the step counters' launch that the lookahead puts right
 		// behind the exchange (a system-scope store, as k_loss_grad's at one rank); otherwise by a copy and an event
 		uint32_t* abort_host_ctr = nullptr;
-		if (risky && coll_on() && la_go) {
+		if (risky && x.on() && la_go) {
 			abort_host_ctr = arm_abort_word();
 			abort_direct = true;
 		}
@@ -1862,7 +1683,7 @@ struct NeusTestbed {
 		// the overlapped exchange (xo): the canonical backward all-reduces its gradient ranges as they finish; opt.adam_overlap
 		// (static scenes; one rank, or behind the overlapped exchange): the optimizer step in pieces beside the scatter
 		AdamSplit asp{};
-		const bool a_over = opt.adam_overlap && !dyn && (!coll_on() || xo);
+		const bool a_over = opt.adam_overlap && !dyn && (!x.on() || xo);
 		if (a_over) asp.p = adam_params();
 		if (use_delta) {
 			// the training forward runs on the deformed batch; dL/d(position) feeds the DeltaNetwork backward
@@ -1886,7 +1707,7 @@ struct NeusTestbed {
 			HIP_CHECK(hipMemcpyAsync(health_buf.p, &st.p->fail_flags, 4, hipMemcpyDeviceToDevice, s));
 			HIP_CHECK(hipMemcpyAsync(health_buf.p + 1, scan_tmp.p + offsetof(ScanState, fail), 4, hipMemcpyDeviceToDevice, s));
 		}
-		if (coll_on()) {
+		if (x.on()) {
 			// collective 1 (gradients; DeltaNetwork partials) and 3 (counters, loss scalars) of SURVEY §8(e). The gradient
 			// of the grid levels past the progressive valid level is zero on every rank: the scatter writes no records there
 			// and keeps that range zeroed (scatter_work_for's sc_zero_from / sc_zero_from_e invariant: every grid entry from
@@ -1894,18 +1715,18 @@ struct NeusTestbed {
 			// tables and the variance move. Overlapped: the gradients went out during the backward (net_backward).
 			const size_t grid_act = 2 * (size_t)gl.offset[std::min(valid + 1, gl.n_levels)];
 			if (xt) HIP_CHECK(hipEventRecord(xt[1].get(), s));  // the backward is done (and the loss sums, when logged)
-			hipStream_t xs = xo ? x_stream() : stream;
-			coll_begin();
+			hipStream_t xs = xo ? x.gated() : stream;
+			x.begin();
 			if (!xo) {
-				allreduce_f32(grads.p, (size_t)lay.grid_off + grid_act);
-				allreduce_f32(grads.p + lay.var_off, lay.P - lay.var_off);
+				x.allreduce_f32(grads.p, (size_t)lay.grid_off + grid_act);
+				x.allreduce_f32(grads.p + lay.var_off, lay.P - lay.var_off);
 			}
-			if (use_delta) allreduce_f32(delta_partial.p, delta_partial_floats(), false, xs);
-			if (get_loss) { allreduce_f32(loss_sum.p, 3, false, xs); allreduce_u32(health_buf.p, 2, xs); }
-			coll_end();
+			if (use_delta) x.allreduce_f32(delta_partial.p, delta_partial_floats(), false, xs);
+			if (get_loss) { x.allreduce_f32(loss_sum.p, 3, false, xs); x.allreduce_u32(health_buf.p, 2, xs); }
+			x.end();
 			if (a_over) adam_issue(asp, lay.P, grads.p, false);  // the optimizer's last piece, behind the exchange
 			if (xt) HIP_CHECK(hipEventRecord(xt[2].get(), xs));
-			x_join();
+			x.join();
 		}
 		if (get_loss) {
 			if (loss_pending) consume_loss();  // (consumed at this step's start already; a restored state may leave one)
@@ -1992,7 +1813,7 @@ struct NeusTestbed {
 		}
 		const StepState& h = prof_st.get()[par];
 		phase_npre += h.n_kept;
-		phase_ntrain += std::min(h.compacted_global / std::max(1u, world), batch);
+		phase_ntrain += std::min(h.compacted_global / std::max(1u, x.world()), batch);
 		++phase_steps;
 		prof_pending[par] = false;
 	}
@@ -2008,7 +1829,7 @@ struct NeusTestbed {
 		HIP_CHECK(hipEventSynchronize(ev_loss.get()));
 		const float* const pin = pinned.get();  // (the readback copies are complete)
 		const StepState* sst = (const StepState*)(pin + 64);
-		const float measured = (float)sst->compacted_global / (float)world;
+		const float measured = (float)sst->compacted_global / (float)x.world();
 		const float scale = measured / (float)batch;
 		last_loss = pin[0] * scale;
 		ek_loss = pin[1] * scale;
@@ -2016,7 +1837,7 @@ struct NeusTestbed {
 		last_rays_with_samples = sst->rays_ws_global;
 		last_keep_ratio = sst->n_kept ? measured / (float)sst->n_kept : 1.f;  // composited / kept (progressive inference)
 		choose_chunk_ends(sst->compacted_global, sst->rays_ws_global);
-		ray_loss = sst->rays_ws_global ? pin[0] * (float)(sst->rays_per_batch * world) / (float)sst->rays_ws_global : 0.f;
+		ray_loss = sst->rays_ws_global ? pin[0] * (float)(sst->rays_per_batch * x.world()) / (float)sst->rays_ws_global : 0.f;
 		if (!loss_ema_init) { loss_scalar_ema = last_loss; loss_ema_init = true; }
 		else loss_scalar_ema = 0.99f * loss_scalar_ema + 0.01f * last_loss;
 		// health: a non-finite loss sum (a NaN / Inf flag on the loss; the sums are all-reduced, so every
@@ -2037,7 +1858,7 @@ struct NeusTestbed {
 		// the words are sums over the ranks, not bit sets: word 0 sums the ranks' fail_flags (the march sets only
 		// STEP_FAIL_MARCH_T there), word 1 the scans' give-up counters; any nonzero sum names its cause
 		const uint32_t global = (all[0] ? STEP_FAIL_MARCH_T : 0u) | (all[1] ? STEP_FAIL_SCAN : 0u);
-		health_raise(local | (coll_on() ? global : 0u), local == 0 && coll_on() && global != 0, raise);
+		health_raise(local | (x.on() ? global : 0u), local == 0 && x.on() && global != 0, raise);
 	}
 	uint32_t fail_seen = 0;
 	void health_raise(uint32_t flags, bool other_rank = false, bool raise = true) {
@@ -2525,7 +2346,7 @@ static void time_kernel_impl(NeusTestbed* tb, int kernel, int variant, int iters
 		if (!tb->have_net) throw std::runtime_error("no network");
 		NeusTestbed& t = *tb;
 		hipStream_t s = t.stream;
-		const DPInfo dp{t.rank, t.world};
+		const DPInfo dp = t.dp_info();
 		const uint32_t valid = t.valid_level_at((int)t.training_step);
 		const uint32_t* lin = t.bf_lin.p;
 		auto march = [&]() {
@@ -2727,7 +2548,7 @@ int neus_debug_march_profile(NeusTestbed* tb, unsigned long long* out, uint32_t 
 		MarchWork mw = t.mwork;
 		mw.prof = buf.p;
 		mw.dbg = t.opt.march_dbg;
-		launch_march_count(s, MAX_RAYS, t.max_samples, t.st.p, DPInfo{t.rank, t.world}, t.ds, t.bitfield.p, t.bf_lin.p, t.rng.state, t.rng.inc,
+		launch_march_count(s, MAX_RAYS, t.max_samples, t.st.p, t.dp_info(), t.ds, t.bitfield.p, t.bf_lin.p, t.rng.state, t.rng.inc,
 		                   t.rays.p, t.startt.p, t.nreq.p, mw, nullptr, 0, t.opt.ray_cull ? t.occ_bbox.p : nullptr);
 		HIP_CHECK(hipStreamSynchronize(s));
 		const uint32_t n = std::min(waves, max_waves);
@@ -2785,20 +2606,11 @@ int neus_testbed_infer_timing(NeusTestbed* tb, double* ms_total, uint64_t* launc
 		if (steps) *steps = tb->it_steps;
 	});
 }
-int neus_testbed_set_exchange_timing(NeusTestbed* tb, int on) {
-	return guard([&] {
-		tb->xt_collect_all();
-		tb->xt_on = on != 0;
-		tb->xt_exposed_ms = tb->xt_span_ms = 0.0; tb->xt_steps = 0;
-	});
-}
+int neus_testbed_set_exchange_timing(NeusTestbed* tb, int on) { return guard([&] { tb->x.set_timing(on != 0); }); }
 int neus_testbed_exchange_timing(NeusTestbed* tb, double* exposed_ms_total, double* span_ms_total, uint64_t* steps) {
 	return guard([&] {
 		HIP_CHECK(hipSetDevice(tb->device));
-		tb->xt_collect_all();
-		if (exposed_ms_total) *exposed_ms_total = tb->xt_exposed_ms;
-		if (span_ms_total) *span_ms_total = tb->xt_span_ms;
-		if (steps) *steps = tb->xt_steps;
+		tb->x.timing(exposed_ms_total, span_ms_total, steps);
 	});
 }
 int neus_testbed_kernel_times(NeusTestbed* tb, float* ms) {
@@ -2811,95 +2623,21 @@ int neus_testbed_kernel_times(NeusTestbed* tb, float* ms) {
 	});
 }
 
-int neus_nccl_unique_id(uint8_t* out) {
-	return guard([&] {
-		ncclUniqueId id;
-		NCCL_CHECK(ncclGetUniqueId(&id));
-		static_assert(sizeof(id) == 128, "ncclUniqueId size");
-		std::memcpy(out, &id, 128);
-	});
-}
+// ------------------------------------------------------------ data parallel (exchange.h; the groups' own entry points: exchange.cpp)
 int neus_testbed_init_data_parallel_ex(NeusTestbed* tb, int rank, int world, const uint8_t* uid, uint32_t flags) {
-	return guard([&] {
-		if (world < 1 || rank < 0 || rank >= world) throw std::runtime_error("invalid rank/world");
-		if (tb->comm || tb->group || tb->hgroup) throw std::runtime_error("init_data_parallel: the testbed already has a communicator");
-		HIP_CHECK(hipSetDevice(tb->device));
-		tb->rank = (uint32_t)rank; tb->world = (uint32_t)world;
-		tb->force_coll = (flags & NEUS_DP_FORCE_COLLECTIVES) != 0;
-		tb->overlap_verified = false;
-		tb->tbuf.indeed_batch = (float)tb->batch * (float)world;
-		tb->coll_calls = tb->coll_bytes = tb->coll_bytes_step = 0;
-		if (world > 1 || tb->force_coll) {
-			if (!uid) throw std::runtime_error("init_data_parallel: no unique id");
-			ncclUniqueId id;
-			std::memcpy(&id, uid, 128);
-			ncclComm_t c = nullptr;
-			NCCL_CHECK(ncclCommInitRank(&c, world, id, rank));
-			tb->comm.reset(c);
-		}
-	});
-}
-int neus_testbed_set_exchange_overlap(NeusTestbed* tb, int on) {
-	return guard([&] {
-		HIP_CHECK(hipStreamSynchronize(tb->stream));
-		tb->exchange_overlap = on != 0;
-		tb->overlap_verified = false;
-	});
+	return guard([&] { tb->attach([&] { tb->x.attach_rccl(tb->device, rank, world, uid, flags); }); });
 }
 int neus_testbed_init_data_parallel(NeusTestbed* tb, int rank, int world, const uint8_t* uid) {
 	return neus_testbed_init_data_parallel_ex(tb, rank, world, uid, 0u);
 }
-int neus_testbed_data_parallel_info(NeusTestbed* tb, NeusDataParallelInfo* o) {
-	return guard([&] {
-		o->rank = tb->rank; o->world = tb->world;
-		o->has_communicator = tb->comm ? 1u : 0u; o->local_group = tb->group ? 1u : 0u; o->host_group = tb->hgroup ? 1u : 0u;
-		o->collective_calls = tb->coll_calls; o->allreduce_bytes = tb->coll_bytes; o->last_step_allreduce_bytes = tb->coll_bytes_step;
-	});
-}
-
-int neus_local_group_create(int world, NeusLocalGroup** out) {
-	return guard([&] {
-		if (world < 1 || world > 64) throw std::runtime_error("local group: world must be 1..64");
-		*out = new NeusLocalGroup((uint32_t)world);
-	});
-}
-int neus_local_group_destroy(NeusLocalGroup* g) { return guard([&] { delete g; }); }
 int neus_testbed_init_local_group(NeusTestbed* tb, NeusLocalGroup* g, int rank) {
-	return guard([&] {
-		if (!g || rank < 0 || (uint32_t)rank >= g->world) throw std::runtime_error("invalid local group / rank");
-		if (tb->comm) throw std::runtime_error("testbed already has an RCCL communicator");
-		tb->group = g; tb->rank = (uint32_t)rank; tb->world = g->world;
-		tb->tbuf.indeed_batch = (float)tb->batch * (float)tb->world;
-		tb->overlap_verified = false;
-	});
-}
-
-int neus_host_group_create(int rank, int world, const char* host, int port, uint64_t job_token, NeusHostGroup** out) {
-	return guard([&] {
-		if (world < 1 || world > 64 || rank < 0 || rank >= world) throw std::runtime_error("host group: world must be 1..64, 0 <= rank < world");
-		if (port <= 0 || port > 65535) throw std::runtime_error("host group: invalid port");
-		*out = new NeusHostGroup(rank, world, host ? host : "127.0.0.1", port, job_token);
-	});
-}
-int neus_host_group_destroy(NeusHostGroup* g) { return guard([&] { delete g; }); }
-int neus_debug_host_group_allreduce(NeusHostGroup* g, void* host, uint64_t n, int type, int op) {
-	return guard([&] {
-		if (!g) throw std::runtime_error("invalid host group");
-		g->allreduce_host(host, (size_t)n * 4, type ? NeusHostGroup::U32 : NeusHostGroup::F32, op ? NeusHostGroup::MAX : NeusHostGroup::SUM);
-		g->check();
-	});
+	return guard([&] { tb->attach([&] { tb->x.attach_local(g, rank); }); });
 }
 int neus_testbed_init_host_group(NeusTestbed* tb, NeusHostGroup* g) {
-	return guard([&] {
-		if (!g) throw std::runtime_error("invalid host group");
-		if (tb->comm || tb->group || tb->hgroup) throw std::runtime_error("init_host_group: the testbed already has a communicator");
-		HIP_CHECK(hipSetDevice(tb->device));
-		tb->hgroup = g; tb->rank = (uint32_t)g->rank; tb->world = (uint32_t)g->world;
-		tb->tbuf.indeed_batch = (float)tb->batch * (float)tb->world;
-		tb->coll_calls = tb->coll_bytes = tb->coll_bytes_step = 0;
-		tb->overlap_verified = false;
-	});
+	return guard([&] { tb->attach([&] { tb->x.attach_host(tb->device, g); }); });
 }
+int neus_testbed_set_exchange_overlap(NeusTestbed* tb, int on) { return guard([&] { tb->x.set_overlap(on != 0); }); }
+int neus_testbed_data_parallel_info(NeusTestbed* tb, NeusDataParallelInfo* o) { return guard([&] { tb->x.info(o); }); }
 
 // ------------------------------------------------------------ operator surface
 int neus_grid_encode(NeusTestbed* tb, void* stream, uint32_t n, uint32_t ld, const float* coords, uint32_t stride, uint32_t valid,
@@ -3073,7 +2811,7 @@ int neus_debug_replay_loss_grad(NeusTestbed* tb, uint16_t* dl_dout_out) {
 		Dev<float> co; co.alloc((size_t)t.batch * COORD_W);
 		Dev<half_t> dl; dl.alloc((size_t)t.batch * OUT_W);
 		HIP_CHECK(hipMemsetAsync(dl.p, 0, dl.n * 2, s));
-		launch_loss_grad(s, t.max_samples, t.st.p, DPInfo{t.rank, t.world}, lp, t.coords.p, t.net_out.p, t.numsteps.p, w, co.p, dl.p);
+		launch_loss_grad(s, t.max_samples, t.st.p, t.dp_info(), lp, t.coords.p, t.net_out.p, t.numsteps.p, w, co.p, dl.p);
 		HIP_CHECK(hipStreamSynchronize(s));
 		HIP_CHECK(hipMemcpy(dl_dout_out, dl.p, dl.n * 2, hipMemcpyDeviceToHost));
 	});
