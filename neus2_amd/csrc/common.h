@@ -175,7 +175,7 @@ struct StepState {
 	// for the backward while the counters update and the next step's sampling can start before the backward ends)
 	uint32_t compacted_global;
 	uint32_t rays_ws_global;
-	// the march cut (testbed.cpp march_cut_for): cut_abort - this step's training is not provably the full
+	// the march cut (step_plan.h plan_sampling: mcut): cut_abort - this step's training is not provably the full
 	// march's (k_loss_grad copies it from the loss's abort word; all-reduced with the two counters above, so every rank
 	// sees the same); while set, the optimizer and the step counters leave every state untouched and the host re-runs the
 	// step with the full march. march_cut - this step's march covered only the slots below the cut estimate. mi_lb - a lower

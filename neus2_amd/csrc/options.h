@@ -38,7 +38,7 @@ struct NeusOptions {
 	// NEUS_MAIN_PRIO=0: the step's streams at the default priority, not the highest. Explicit priorities keep a testbed created
 	// after another was destroyed at 1.24 ms/step (16-level leg) where the default ran 1.91 (profiles/r05l16_priorities_ab.txt)
 	bool main_prio = true;
-	// NEUS_LOOKAHEAD=0: no sampling of the next step beside this step's backward (A/B reference; train_step: la_go)
+	// NEUS_LOOKAHEAD=0: no sampling of the next step beside this step's backward (A/B reference; step_plan.h StepPlan::la_go)
 	bool lookahead = true;
 	// NEUS_LA_AT: where in the backward a cut march's lookahead is issued (NeusTestbed::la_at). 1, after the encode: 0.770 ->
 	// 0.759 ms/step at step 800, 0.876 -> 0.854 at step 1600 against 0 (profiles/r06la_issue_point_ab.txt)
@@ -78,9 +78,9 @@ struct NeusOptions {
 	bool ray_cull = true;
 	// NEUS_RAY_SORT=0: the progressive rounds' rays in slot order, not the spatial order (A/B reference)
 	bool ray_sort = true;
-	// NEUS_PROG_CUT=0: no compaction cut (A/B reference; NeusTestbed::cut_for)
+	// NEUS_PROG_CUT=0: no compaction cut (A/B reference; step_plan.h plan_sampling: cut)
 	bool prog_cut = true;
-	// NEUS_MARCH_CUT=0: no march cut (A/B reference; NeusTestbed::march_cut_for)
+	// NEUS_MARCH_CUT=0: no march cut (A/B reference; step_plan.h plan_sampling: mcut)
 	bool march_cut = true;
 	// NEUS_DBG_MARCH_CUT_DIV: test hook, at least 1; divides the march cut's estimate so that witnesses fail and steps re-run
 	uint32_t march_cut_div = 1;

@@ -16,6 +16,7 @@
 #include "scan_lookback.h"
 #include "json_lite.h"
 #include "options.h"
+#include "step_plan.h"
 #include "host_util.h"
 #include "exchange.h"
 #include "core.h"
@@ -116,8 +117,7 @@ struct NeusTestbed {
 	// Lookahead (opt.lookahead): the next step's ray sampling (ray generation, march, march write, ray sort) issued on
 	// la_stream behind this step's counters (their stream: the step's, or the exchange stream with a group), beside its
 	// backward and optimizer, which read none of its outputs. At any world size; only between steps of one
-	// neus_testbed_train call (nothing pending between calls), on static scenes, and not before a step that starts with an
-	// occupancy update or a loss readback (train_step: la_go).
+	// neus_testbed_train call (nothing pending between calls); which steps look ahead: step_plan.h StepPlan::la_go.
 	// opt.adam_overlap: the step's Adam parameters; next: the first parameter not issued; on: the exchange stream the pieces
 	// follow their ranges' all-reduces on (data parallel), or null (one rank: ad_stream, behind the step's stream)
 	struct AdamSplit { AdamParams p; uint32_t next; hipStream_t on; };
@@ -276,33 +276,8 @@ struct NeusTestbed {
 	Dev<float> l_ekt, l_cke, l_rT, l_rek;
 	Dev<uint32_t> sample_ray;
 	Dev<uint32_t> cmap;  // compacted sample -> ray (LossWork::cmap)
-	// progressive (cut-off-aware) inference: 0 off, 1 auto (when under PROGRESSIVE_RATIO of the kept samples were
-	// composited at the last loss readback), 2 always; chunk ends of the rounds before the last (march.hip)
-	int progressive_mode = 1;
-	std::vector<uint32_t> chunk_ends = opt.chunk_ends.empty() ? std::vector<uint32_t>{32, 64, 96} : opt.chunk_ends;
-	std::vector<uint32_t> chunk_ends_cut;  // the chunk ends of a cut step (chosen with chunk_ends; empty: chunk_ends)
-	const std::vector<uint32_t>& ends_for(bool cut) const { return cut && !chunk_ends_cut.empty() ? chunk_ends_cut : chunk_ends; }
-	// Chunk ends chosen from the training state (chunk_auto: no explicit ends given): at each loss readback the mean
-	// composited samples per ray with samples, mc (all-reduced counters: the same on every rank), sets three rounds
-	// {e, 2e, rest} with e = 0.5 mc + 12 rounded to 8 in [24, 128]. Measured at the bench workload (Config S, R = Nc =
-	// 2^18, profiles/r04fg_chunk_ends_sweep.txt, r04hi_*): step 800 (mc ~117) best at e = 64 (1.237 ms vs 1.283 for
-	// {32, 64, 96}), step 1600 (mc ~39) best at e = 32 (1.203 ms vs 1.308 for e = 64). The rounds only change which
-	// samples are evaluated, never a result (bit-identical to the one pass).
-	bool chunk_auto = opt.chunk_ends.empty();
-	void choose_chunk_ends(uint32_t composited, uint32_t rays_with_samples) {
-		if (!chunk_auto || rays_with_samples == 0) return;
-		const float mc = (float)composited / (float)rays_with_samples;
-		const uint32_t e = std::min(128u, std::max(24u, 8u * (uint32_t)std::lround((0.5f * mc + 12.f) / 8.f)));
-		chunk_ends.assign({e, 2 * e});
-		// With the compaction cut (and the march cut) the later rounds see only the rays before the cut (a few thousand at
-		// the bench's shape), so their fixed cost - launches, scans, the cut - outweighs the samples a third round saves:
-		// two rounds, the first twice as long (opt.chunk_scale, opt.chunk_rounds).
-		const uint32_t ec = std::min(256u, std::max(24u, 8u * (uint32_t)std::lround(opt.chunk_scale * (0.5f * mc + 12.f) / 8.f)));
-		if (opt.chunk_rounds == 2) chunk_ends_cut.assign({ec});
-		else chunk_ends_cut.assign({ec, 2 * ec});
-	}
-	float last_keep_ratio = 1.f;
-	static constexpr float PROGRESSIVE_RATIO = 0.7f;
+	// progressive (cut-off-aware) inference: its mode, the rounds' chunk ends and the rule that chooses them (step_plan.h)
+	ChunkSchedule sched{opt};
 	Dev<uint32_t> chunk_list, chunk_cnt;  // chunk_cnt: [k] round k's sample list length, [16] the long-ray list's, [32 + k] open rays
 	Dev<uint32_t> open_rays[2];          // the rays still open after a round (ping-pong: round k reads [(k - 1) & 1])
 	// spatial ray order of the progressive rounds (RaySort; without opt.ray_sort: slot order, one-XCD-agnostic lists)
@@ -314,20 +289,15 @@ struct NeusTestbed {
 	// The compaction cut (march.hip k_prog_cut): with fixed rays per batch the later progressive rounds skip the rays whose
 	// compaction base is already past the batch after a round. Training is bitwise the same; what changes is the summed
 	// composited count of such a step (a lower bound, still >= the batch), which with fixed rays feeds no result - only the
-	// logged loss scale, the chunk-end rule and the stats. So a step that the host reads back (a loss readback step, the last
-	// step of a train call) never cuts, and every value the host sees is the uncut one. Off without opt.prog_cut.
+	// logged loss scale, the chunk-end rule and the stats. Which steps cut: step_plan.h plan_sampling (none that the host
+	// reads back, so every value the host sees is the uncut one).
 	// With the spatial ray order, round 0 itself is split too: the sort puts the rays of the slots below the previous step's
 	// cut (+ 1/4, + 1024: cutw[CW_EST]) first (pass A); once pass A is scanned the cut is known whenever the prefix reaches
 	// the batch in those slots, and pass B (the rest of round 0) then has nothing to do.
 	Dev<uint32_t> open_raw, cutw;  // the rays open after round 0, before the cut; the cut words (kernels.h CW_*)
 	uint64_t cut_steps = 0;
 	uint32_t call_left = 0;        // steps of the current train call after the current one
-	bool la_cut = false;           // the pending lookahead's step cuts (its sort was split)
-	bool la_mcut = false;          // the pending lookahead's march was cut (march_cut_for)
-	bool cut_for(uint32_t step, bool progressive, bool last_in_call, bool dyn) const {
-		const uint32_t nch = (uint32_t)chunk_ends.size() + 1;
-		return opt.prog_cut && progressive && cfg.fixed_rays_per_batch && !dyn && step % 16 != 0 && !last_in_call && nch >= 2 && nch <= 15;
-	}
+	SamplingPlan la_plan;          // the sampling the pending lookahead issued: the next step's, which uses it whole
 	// The march cut: on a cut step the compaction cut lies, nearly always, well inside the slots below the
 	// split estimate (cutw[CW_EST]: at the bench's step 800, 5.6 K of the 41 K kept slots), and no ray past it contributes a
 	// training sample. So such a step generates and marches only those slots (MarchWork::est_cut). Two things make that
@@ -338,9 +308,8 @@ struct NeusTestbed {
 	// the optimizer and the step counters of that step then change nothing, the host sees the word before it queues the
 	// next step, restores its own state to the step's start and runs the step again with the full march (after recounting
 	// the step before it in full when that one was cut, which makes its cap exact). The trained parameters are those of
-	// the full march in every case. A step the host reads back, one with (or before) an occupancy update, and the last two
-	// steps of a train call never cut the march, so the loss readback and the end of a call need no extra wait.
-	// Off without opt.march_cut.
+	// the full march in every case. Which steps cut the march: step_plan.h plan_sampling (chosen so that the loss readback
+	// and the end of a call need no extra wait).
 	bool force_full = false;      // the step being re-run marches every slot
 	Dev<uint32_t> occ_nu_key, occ_nu_list, occ_nu_bins;  // opt.occ_nu_sort: the occupancy-biased samples binned by their coarse cell
 	bool abort_direct = false;            // the last risky step's word comes through abort_word (one rank)
@@ -358,11 +327,6 @@ struct NeusTestbed {
 	Event ev_abort, ev_abort_src;
 	uint64_t mcut_steps = 0, mcut_reruns = 0;
 	Dev<StepState> st_recount;
-	static bool occ_at(uint32_t cs) { const uint32_t n_prep = std::min(16u, std::max(1u, cs / 16u)); return cs % n_prep == 0; }
-	bool march_cut_for(uint32_t step, bool cut, uint32_t left_at_step) const {
-		if (!opt.march_cut || force_full || !cut || profiling || !mwork.balanced || mwork.lanes_per_ray != 8 || ds.cone_angle != 0.0f) return false;
-		return (step + 1) % 16 != 0 && left_at_step >= 2 && !occ_at(step) && !occ_at(step + 1);
-	}
 	Dev<uint32_t> long_rays;  // the loss scan's wave-per-ray list (+ its counter in chunk_cnt[16])
 	TrainBufs tbuf{};
 	// RNG + counters (testbed.cu:2087-2101)
@@ -1434,7 +1398,7 @@ struct NeusTestbed {
 		// the readback of 16 steps back (long done on the device) is checked at this step boundary, before anything of
 		// this step is queued: a health failure (all-reduced, so every rank sees it) stops every rank on the same step
 		// with no collective half-issued and no step half-applied; the host stays at most 16 steps ahead of the device
-		if (training_step % 16 == 0 && loss_pending) consume_loss();
+		if (readback_at(training_step) && loss_pending) consume_loss();
 		// dynamic scenes (testbed.cu:2651-2712): progressive levels count from the end of the global-movement
 		// phase; at its end canonical training starts (and the movement keeps training when finetuned)
 		const bool dyn = cur_frame >= 1;
@@ -1453,41 +1417,38 @@ struct NeusTestbed {
 		enc_step = dyn ? (int)training_step - (int)gm_steps() : (int)training_step;
 		const uint32_t valid = valid_level_at(enc_step);
 		if (use_delta) launch_delta_prepare(s, delta.p);
-		const uint32_t n_prep = std::min(16u, std::max(1u, canonical_step / 16u));
+		// every decision about this step's shape, from the host state as it stands here (step_plan.h); a step whose samples
+		// came from the previous step's lookahead takes the sampling that lookahead planned and issued
+		StepFacts facts;
+		facts.step = training_step; facts.canonical_step = canonical_step; facts.left = call_left; facts.next_in_call = la_next_in_call;
+		facts.dyn = dyn; facts.use_delta = use_delta; facts.train_canonical = train_canonical;
+		facts.fixed_rays = cfg.fixed_rays_per_batch; facts.profiling = profiling;
+		facts.balanced = mwork.balanced; facts.lanes_per_ray = mwork.lanes_per_ray; facts.cone_angle = ds.cone_angle;
+		facts.occ_cells = GRID3 * (max_cascade + 1);
+		facts.force_full = force_full; facts.prev_mcut = mc_hist[1]; facts.loss_pending = loss_pending;
+		facts.dbg_hook = dbg_lds_fill || g_dbg_lds_fill != 0 || g_dbg_xcd_shift != 0;
+		facts.x_on = x.on(); facts.x_overlap = x.overlap();
+		const StepPlan p = la_have ? plan_step(opt, facts, la_plan) : plan_step(opt, sched, facts);
+		const SamplingPlan& sp = p.sampling;
 		mark(0);
-		if (canonical_step % n_prep == 0) {
-			const uint32_t nc = GRID3 * (max_cascade + 1);
-			if (training_step < 256) occ_update(nc, 0, valid, use_delta);
-			else occ_update(nc / 4, nc / 4, valid, use_delta);
-		}
+		if (p.occ_update) occ_update(p.occ_uniform, p.occ_nonuniform, valid, use_delta);
 		// ---- train_nerf_step (testbed_nerf.cu:3723-4001)
 		if (training_step == 0 || canonical_step == 0) HIP_CHECK(hipMemsetAsync(&st.p->n_rays_total, 0, 4, s));
 		const uint32_t world = x.world();
 		const DPInfo dp = dp_info();  // (n_kept, n_rays_with_samples: zeroed by k_ray_gen)
 		mark(1);
-		// progressive (cut-off-aware) inference this step: its round-0 list is written by the march
-		const bool progressive = progressive_mode == 2 || (progressive_mode == 1 && last_keep_ratio < PROGRESSIVE_RATIO);
-		const bool sorted_rays = progressive && opt.ray_sort;  // round 0's list by k_ray_sort_place instead of the march write
 		const RaySort rsort{rs_hist.p, rs_off.p, rs_key.p, rs_perm.p, chunk_cnt.p + RS_N_PERM};
 		if (la_have) {
-			if (canonical_step % n_prep == 0) throw std::runtime_error("train: lookahead issued before an occupancy update");
+			if (p.occ_update) throw std::runtime_error("train: lookahead issued before an occupancy update");
 			++la_steps;
 			if (opt.la_stat && la_stat_used % 4 == 2) HIP_CHECK(hipEventRecord(la_stat_next(), s));
 			HIP_CHECK(hipStreamWaitEvent(s, ev_la_done.get(), 0));  // this step's samples came from the previous step's lookahead
 			if (opt.la_stat && la_stat_used % 4 == 3) HIP_CHECK(hipEventRecord(la_stat_next(), s));
 		}
-		const bool cut = la_have ? la_cut : cut_for(training_step, progressive, call_left == 0, dyn);
-		const std::vector<uint32_t>& ce = ends_for(cut);  // (a cut step's rounds: chunk_ends_cut)
-		const uint32_t nch = (uint32_t)ce.size() + 1;
-		const bool mcut = la_have ? la_mcut : march_cut_for(training_step, cut && sorted_rays, call_left);
-		if (!la_have) issue_march(s, dp, rng, progressive, scan_tmp.p, cut, mcut);
-		mc_hist[0] = mcut;
-		// (this step's witness can fail: the host waits for its word; a re-run step is exact by construction - not cut, and
-		// the step before it recounted when that one was cut)
-		const bool risky = (mc_hist[0] || mc_hist[1]) && !force_full;
-		const bool split = cut && sorted_rays;
-		if (cut) ++cut_steps;
-		if (mcut) ++mcut_steps;
+		if (!la_have) issue_march(s, dp, rng, sp, scan_tmp.p);
+		mc_hist[0] = sp.mcut;
+		if (sp.cut) ++cut_steps;
+		if (sp.mcut) ++mcut_steps;
 		mark(2);
 		// DeltaNetwork forward on the samples (nerf_network.h:162-182); the loss keeps the undeformed records
 		const float* c_in = coords.p;
@@ -1496,26 +1457,22 @@ struct NeusTestbed {
 		lp.loss_scale = LOSS_SCALE; lp.ek_w = cfg.ek_loss_weight; lp.mask_w = cfg.mask_loss_weight; lp.cos_anneal = cos_anneal();
 		lp.max_compacted = batch; lp.rng_state = rng.state; lp.rng_inc = rng.inc; lp.jt = jump_table();
 		lp.abort_w = cutw.p + CW_ABORT; lp.abort_slot = training_step & 1u;
-		if (risky && !x.on()) {
+		if (p.risky && !x.on()) {
 			// one rank: the word goes straight from k_loss_grad to host memory (no copy, no event on the step's streams)
 			lp.abort_host = arm_abort_word();
 		}
 		lp.dbg_fence = opt.dbg_loss_fence ? 1u : 0u;
 		const LossWork w = loss_work(base.p);
-		if (progressive) {
+		if (sp.progressive) {
 			// rounds of per-ray chunks, each: network on the round's samples, alpha, the recurrence continued (march.hip);
 			// the "infer" phase mark then covers the composite as well
 			uint32_t e0 = 0;
-			// the chunk scans' form (opt.scan_form): 16 lanes per ray on a cut step, whose rounds visit a few thousand
-			// rays with chunks of 64 samples and more; one lane per ray on every other step (many rays, short chunks)
-			const bool scan_group = opt.scan_form == 2 || (opt.scan_form == 0 && cut);
-			// the compaction cut (opt.prog_cut, cut_for): fixed rays per batch, not a step the host reads back (the loss readback
-			// steps, the last step of a train call), one rank's own batch
+			const uint32_t nch = sp.nch;
 			for (uint32_t k = 0; k < nch; ++k) {
-				const uint32_t e1 = k + 1 < nch ? ce[k] : 0xffffffffu;
-				const uint32_t e2 = k + 2 < nch ? ce[k + 1] : 0xffffffffu;
+				const uint32_t e1 = k + 1 < nch ? sp.ends[k] : 0xffffffffu;
+				const uint32_t e2 = k + 2 < nch ? sp.ends[k + 1] : 0xffffffffu;
 				// the loss's alpha terms in the inference epilogue (k_loss_alpha's work on the round's samples)
-				const InferAlpha ia{w.sa, w.ekt, lp.cos_anneal, ds.cone_angle == 0.0f ? 1u : 0u, nullptr, sorted_rays ? 8u : 0u};
+				const InferAlpha ia{w.sa, w.ekt, lp.cos_anneal, ds.cone_angle == 0.0f ? 1u : 0u, nullptr, sp.sorted_rays ? 8u : 0u};
 				it_arm();
 				launch_nerf_infer(s, lay.L, lay.W, chunk_cnt.p + k, 0, c_in, gl, valid, params_h.p + lay.grid_off, mlp, net_out.p, 8192, chunk_list.p,
 				                  use_delta ? nullptr : &ia);
@@ -1523,18 +1480,18 @@ struct NeusTestbed {
 				const bool more = k + 1 < nch;
 				// the cut after round 0 (the rays of the later rounds are then all at or before it: each round continues
 				// only the rays of the round before it)
-				const bool cut_k = cut && k == 0 && more;
+				const bool cut_k = sp.cut && k == 0 && more;
 				launch_loss_scan_chunk(s, MAX_RAYS, numsteps.p, w, ccount.p, e0, e1, e2, more && !cut_k ? chunk_list.p : nullptr, chunk_cnt.p + k + 1,
-				                       k ? open_rays[(k - 1) & 1].p : (sorted_rays ? rs_perm.p : nullptr),
-				                       k ? chunk_cnt.p + OPEN_CNT + k - 1 : (sorted_rays ? rsort.n_perm : nullptr),
+				                       k ? open_rays[(k - 1) & 1].p : (sp.sorted_rays ? rs_perm.p : nullptr),
+				                       k ? chunk_cnt.p + OPEN_CNT + k - 1 : (sp.sorted_rays ? rsort.n_perm : nullptr),
 				                       more ? (cut_k ? open_raw.p : open_rays[k & 1].p) : nullptr,
-				                       more ? chunk_cnt.p + (cut_k ? RAW_CNT : OPEN_CNT) + k : nullptr, scan_group);
+				                       more ? chunk_cnt.p + (cut_k ? RAW_CNT : OPEN_CNT) + k : nullptr, p.scan_group);
 				if (cut_k) {
 					// the cut after this round (cbase as the scan's scratch: the compaction rewrites it after the rounds), then
 					// the next round's rays and samples from the open rays at or before it
 					// a cut march's step: pass B (the slots past the estimate) was not marched, so it is skipped; pass A's
 					// slots must reach the batch, or the step is re-run (the witness word, set by the cut below)
-					const bool split_b = split && !mcut;
+					const bool split_b = p.split && !sp.mcut;
 					if (split_b) {
 						// pass A was the rays below the estimate: its cut, then pass B (empty when the cut lies in pass A's slots)
 						launch_scan_prog_cut(s, scan_tmp.p, ccount.p, cbase.p, MAX_RAYS, batch, cutw.p, 0, nullptr);
@@ -1543,10 +1500,10 @@ struct NeusTestbed {
 						launch_nerf_infer(s, lay.L, lay.W, cutw.p + CW_LENB_EFF, 0, c_in, gl, valid, params_h.p + lay.grid_off, mlp, net_out.p, 8192,
 						                  chunk_list.p + max_samples, &iab);
 						launch_loss_scan_chunk(s, MAX_RAYS, numsteps.p, w, ccount.p, 0, e1, e2, nullptr, nullptr, rs_perm.p + MAX_RAYS,
-						                       cutw.p + CW_NB_EFF, open_raw.p, chunk_cnt.p + RAW_CNT + k, scan_group);
+						                       cutw.p + CW_NB_EFF, open_raw.p, chunk_cnt.p + RAW_CNT + k, p.scan_group);
 					}
 					launch_scan_prog_cut(s, scan_tmp.p, ccount.p, cbase.p, MAX_RAYS, batch, cutw.p, 1, split_b ? chunk_cnt.p : nullptr,
-					                     mcut ? cutw.p + CW_ABORT + (training_step & 1u) : nullptr);
+					                     sp.mcut ? cutw.p + CW_ABORT + (training_step & 1u) : nullptr);
 					launch_prog_next(s, MAX_RAYS, open_raw.p, chunk_cnt.p + RAW_CNT + k, numsteps.p, cutw.p + CW_CUT, e1, e2, chunk_list.p,
 					                 chunk_cnt.p + k + 1, open_rays[k & 1].p, chunk_cnt.p + OPEN_CNT + k);
 				}
@@ -1582,38 +1539,31 @@ struct NeusTestbed {
 		// right after the loss into StepState::compacted_global / rays_ws_global (compacted_counter stays this rank's
 		// training batch for the backward). On the communication stream with the overlapped exchange, so the backward
 		// does not wait for it; the gradients' collectives follow on the same stream, in the same order on every rank.
-		const bool xo = x.on() && x.overlap() && (!dyn || train_canonical);
 		x.reset_step_bytes();
 		hipStream_t cs = s;  // the stream the counters (and the lookahead's start) are ordered on
 		Event* xt = x.timing_slot();
 		if (xt) HIP_CHECK(hipEventRecord(xt[0].get(), s));
 		if (x.on()) {
-			cs = xo ? x.gated() : stream;
+			cs = p.xo ? x.gated() : stream;
 			x.begin();
 			x.allreduce_u32(&st.p->compacted_global, 3, cs);  // (+ cut_abort: every rank re-runs the step, or none)
 			x.end();
 		}
-		if (risky) {
+		if (p.risky) {
 			abort_pending = true;
 			abort_direct = !x.on();
 		}
 		// ---- lookahead: the next step's ray sampling beside this step's backward (opt.lookahead; see the members)
-		const bool get_loss = training_step % 16 == 0;
-		const StepCounterArgs sca{st.p, batch, max_samples, world, cfg.fixed_rays_per_batch, progressive ? chunk_cnt.p : nullptr, nch};
+		const StepCounterArgs sca{st.p, batch, max_samples, world, cfg.fixed_rays_per_batch, sp.progressive ? chunk_cnt.p : nullptr, sp.nch};
 		bool counters_done = false;
-		const uint32_t cs1 = training_step + 1;  // the next step's canonical step (static scenes)
-		const uint32_t n_prep1 = std::min(16u, std::max(1u, cs1 / 16u));
-		const bool la_go = opt.lookahead && la_next_in_call && !dyn && !use_delta && !profiling && !opt.dbg_loss_replay &&
-		                   !dbg_lds_fill && g_dbg_lds_fill == 0 && g_dbg_xcd_shift == 0 && cs1 % 16 != 0 && cs1 % n_prep1 != 0 &&
-		                   !(get_loss && loss_pending);
 		// with a group, the all-reduced word goes to the host from the step counters' launch that the lookahead puts right
 		// behind the exchange (a system-scope store, as k_loss_grad's at one rank); otherwise by a copy and an event
 		uint32_t* abort_host_ctr = nullptr;
-		if (risky && x.on() && la_go) {
+		if (p.risky && x.on() && p.la_go) {
 			abort_host_ctr = arm_abort_word();
 			abort_direct = true;
 		}
-		if (risky && !abort_direct) {
+		if (p.risky && !abort_direct) {
 			// the all-reduced abort word to the host, off the step's stream (the backward starts at once)
 			if (!ev_abort) {
 				ev_abort = make_event(hipEventDisableTiming);
@@ -1627,11 +1577,11 @@ struct NeusTestbed {
 			abort_pending = true;
 		}
 		{
-			if (la_go) {
+			if (p.la_go) {
 				// the host's StepState readback first (its place in the step without the lookahead: nothing it reads is
 				// written between here and there - the ranks' counts are already summed), then the step counters the next
 				// step's sampling reads; both behind the counters' exchange (cs)
-				if (get_loss) HIP_CHECK(hipMemcpyAsync(pinned.get() + 64, st.p, sizeof(StepState), hipMemcpyDeviceToHost, cs));
+				if (p.get_loss) HIP_CHECK(hipMemcpyAsync(pinned.get() + 64, st.p, sizeof(StepState), hipMemcpyDeviceToHost, cs));
 				launch_step_counters(cs, st.p, batch, max_samples, world, cfg.fixed_rays_per_batch, sca.eval_cnt, sca.n_eval, abort_host_ctr);
 				counters_done = true;
 				if (!la_stream) {
@@ -1654,17 +1604,20 @@ struct NeusTestbed {
 				}
 				pcg32 r1 = rng;
 				r1.advance();
-				const bool prog1 = progressive_mode == 2 || (progressive_mode == 1 && last_keep_ratio < PROGRESSIVE_RATIO);
-				la_cut = cut_for(training_step + 1, prog1, call_left <= 1, false);
-				la_mcut = march_cut_for(training_step + 1, la_cut && opt.ray_sort, call_left - 1);
-				const bool cut1 = la_cut, mcut1 = la_mcut;
-				la_at = mcut1 ? opt.la_at_cut : opt.la_at_full;
-				la_deferred = [this, cs, dp, r1, prog1, cut1, mcut1] {
+				// The next step's sampling, planned here and used whole by that step. It is the plan that step would make for
+				// itself: its facts are these with the counters moved on, and the schedule cannot change in between - only a
+				// loss readback changes it, and la_go excludes a next step that starts with one (or with an occupancy update)
+				// and a readback still pending on this one. One exception, as it always was: a re-run step (force_full) hands
+				// its force_full on through next(), so the step after a re-run never cuts its march, where on its own it might.
+				la_plan = plan_step(opt, sched, facts.next()).sampling;
+				const SamplingPlan sp1 = la_plan;
+				la_at = sp1.mcut ? opt.la_at_cut : opt.la_at_full;
+				la_deferred = [this, cs, dp, r1, sp1] {
 					hipStream_t ls = la_stream.get();
 					HIP_CHECK(hipEventRecord(ev_la_start.get(), cs));
 					HIP_CHECK(hipStreamWaitEvent(ls, ev_la_start.get(), 0));
 					if (opt.la_stat) { la_stat_used -= la_stat_used % 4; HIP_CHECK(hipEventRecord(la_stat_next(), ls)); }
-					issue_march(ls, dp, r1, prog1, scan_tmp_la.p, cut1, mcut1);
+					issue_march(ls, dp, r1, sp1, scan_tmp_la.p);
 					if (opt.la_stat) HIP_CHECK(hipEventRecord(la_stat_next(), ls));
 					HIP_CHECK(hipEventRecord(ev_la_done.get(), ls));
 				};
@@ -1678,28 +1631,27 @@ struct NeusTestbed {
 		const EncodeRollover ro{&st.p->compacted_counter, batch, dL_dout.p, coords_c.p};
 		// the canonical backward writes every gradient entry (weight tiles and variance by k_wgrad_reduce, every grid
 		// entry by k_scatter_accum, zeros with no samples); the global-movement phase skips it: zero the buffer there
-		if (!(!dyn || train_canonical)) HIP_CHECK(hipMemsetAsync(grads.p, 0, (size_t)lay.P * 4, s));
+		if (!p.canon_opt) HIP_CHECK(hipMemsetAsync(grads.p, 0, (size_t)lay.P * 4, s));
 		mark(4);
-		// the overlapped exchange (xo): the canonical backward all-reduces its gradient ranges as they finish; opt.adam_overlap
+		// the overlapped exchange (p.xo): the canonical backward all-reduces its gradient ranges as they finish; opt.adam_overlap
 		// (static scenes; one rank, or behind the overlapped exchange): the optimizer step in pieces beside the scatter
 		AdamSplit asp{};
-		const bool a_over = opt.adam_overlap && !dyn && (!x.on() || xo);
-		if (a_over) asp.p = adam_params();
+		if (p.a_over) asp.p = adam_params();
 		if (use_delta) {
 			// the training forward runs on the deformed batch; dL/d(position) feeds the DeltaNetwork backward
 			launch_delta_apply(s, nullptr, batch, COORD_W, coords_c.p, coords_cdef.p, delta.p);
 			tbuf.dpos = dpos.p;
-			net_backward(&st.p->compacted_counter, &st.p->n_train, batch, coords_cdef.p, valid, dL_dout.p, grads.p, s, true, train_canonical, nullptr, xo);
+			net_backward(&st.p->compacted_counter, &st.p->n_train, batch, coords_cdef.p, valid, dL_dout.p, grads.p, s, true, train_canonical, nullptr, p.xo);
 			tbuf.dpos = nullptr;
 		} else {
-			net_backward(&st.p->compacted_counter, &st.p->n_train, batch, coords_c.p, valid, dL_dout.p, grads.p, s, true, train_canonical, &ro, xo,
-			             a_over ? &asp : nullptr);
+			net_backward(&st.p->compacted_counter, &st.p->n_train, batch, coords_c.p, valid, dL_dout.p, grads.p, s, true, train_canonical, &ro, p.xo,
+			             p.a_over ? &asp : nullptr);
 		}
 		la_fire(99);  // (issued by now in any case)
 		// DeltaNetwork gradient partial sums (the first half of its backward; the Adam step follows the exchange)
 		if (use_delta) launch_delta_grad(s, &st.p->n_train, batch, coords_c.p, COORD_W, dpos.p, delta.p, delta_partial.p);
 		mark(8);
-		if (get_loss) {
+		if (p.get_loss) {
 			launch_sum_f32(s, scan_tmp.p, scan_tmp_bytes, loss.p, loss_sum.p + 0, MAX_RAYS);
 			launch_sum_f32(s, scan_tmp.p, scan_tmp_bytes, ek.p, loss_sum.p + 1, MAX_RAYS);
 			launch_sum_f32(s, scan_tmp.p, scan_tmp_bytes, mask.p, loss_sum.p + 2, MAX_RAYS);
@@ -1715,20 +1667,20 @@ struct NeusTestbed {
 			// tables and the variance move. Overlapped: the gradients went out during the backward (net_backward).
 			const size_t grid_act = 2 * (size_t)gl.offset[std::min(valid + 1, gl.n_levels)];
 			if (xt) HIP_CHECK(hipEventRecord(xt[1].get(), s));  // the backward is done (and the loss sums, when logged)
-			hipStream_t xs = xo ? x.gated() : stream;
+			hipStream_t xs = p.xo ? x.gated() : stream;
 			x.begin();
-			if (!xo) {
+			if (!p.xo) {
 				x.allreduce_f32(grads.p, (size_t)lay.grid_off + grid_act);
 				x.allreduce_f32(grads.p + lay.var_off, lay.P - lay.var_off);
 			}
 			if (use_delta) x.allreduce_f32(delta_partial.p, delta_partial_floats(), false, xs);
-			if (get_loss) { x.allreduce_f32(loss_sum.p, 3, false, xs); x.allreduce_u32(health_buf.p, 2, xs); }
+			if (p.get_loss) { x.allreduce_f32(loss_sum.p, 3, false, xs); x.allreduce_u32(health_buf.p, 2, xs); }
 			x.end();
-			if (a_over) adam_issue(asp, lay.P, grads.p, false);  // the optimizer's last piece, behind the exchange
+			if (p.a_over) adam_issue(asp, lay.P, grads.p, false);  // the optimizer's last piece, behind the exchange
 			if (xt) HIP_CHECK(hipEventRecord(xt[2].get(), xs));
 			x.join();
 		}
-		if (get_loss) {
+		if (p.get_loss) {
 			if (loss_pending) consume_loss();  // (consumed at this step's start already; a restored state may leave one)
 			HIP_CHECK(hipMemcpyAsync(pinned.get(), loss_sum.p, 3 * 4, hipMemcpyDeviceToHost, s));
 			HIP_CHECK(hipMemcpyAsync(pinned.get() + 52, health_buf.p, 8, hipMemcpyDeviceToHost, s));
@@ -1739,16 +1691,15 @@ struct NeusTestbed {
 		}
 		// the step-end counters ride on the Adam launch when the canonical optimizer steps (k_step_counters otherwise)
 		// (progressive inference: the samples evaluated are the rounds' list lengths chunk_cnt[0, nch))
-		const bool canon_opt = !dyn || train_canonical;
-		if (!canon_opt && !counters_done) launch_step_counters(s, st.p, batch, max_samples, world, cfg.fixed_rays_per_batch, sca.eval_cnt, sca.n_eval);
+		if (!p.canon_opt && !counters_done) launch_step_counters(s, st.p, batch, max_samples, world, cfg.fixed_rays_per_batch, sca.eval_cnt, sca.n_eval);
 		rng.advance();
 		mark(9);
 		// ---- optimizers (testbed_nerf.cu:3503-3508): the canonical trainer, the global-move trainer
-		if (canon_opt && a_over) {
+		if (p.canon_opt && p.a_over) {
 			++adam_split_steps;
 			if (!counters_done) launch_step_counters(s, st.p, batch, max_samples, world, cfg.fixed_rays_per_batch, sca.eval_cnt, sca.n_eval);
 			adam_join(asp, grads.p);
-		} else if (canon_opt) {
+		} else if (p.canon_opt) {
 			optimizer_step(grads.p, counters_done ? nullptr : &sca);
 		}
 		if (use_delta) {
@@ -1776,24 +1727,21 @@ struct NeusTestbed {
 	}
 
 	// A step's ray sampling: ray generation + the march's two passes, the coordinate write (and round 0's list, unsorted
-	// progressive), the spatial ray sort (sorted progressive); rng / progressive: the step's own (train_step, or the
+	// progressive), the spatial ray sort (sorted progressive); rng / sp: the step's own (train_step, or the
 	// lookahead for the next step), scan: the look-back state of the stream it runs on.
-	void issue_march(hipStream_t s, const DPInfo& dp, const pcg32& r, bool progressive, uint8_t* scan, bool cut = false, bool mcut = false) {
-		const std::vector<uint32_t>& ce = ends_for(cut);
-		const uint32_t nch = (uint32_t)ce.size() + 1;
-		const Round0List r0{ce[0], cbase.p, chunk_list.p, chunk_cnt.p, nch + 1};
-		const bool sorted_rays = progressive && opt.ray_sort;
+	void issue_march(hipStream_t s, const DPInfo& dp, const pcg32& r, const SamplingPlan& sp, uint8_t* scan) {
+		const Round0List r0{sp.ends[0], cbase.p, chunk_list.p, chunk_cnt.p, sp.nch + 1};
 		MarchWork mw = mwork;
-		if (mcut) mw.est_cut = cutw.p + CW_EST;  // (the split sort's estimate: pass A's slots are the marched ones)
+		if (sp.mcut) mw.est_cut = cutw.p + CW_EST;  // (the split sort's estimate: pass A's slots are the marched ones)
 		mw.est_div = opt.march_cut_div;
 		launch_march_count(s, MAX_RAYS, max_samples, st.p, dp, ds, bitfield.p, bf_lin.p, r.state, r.inc, rays.p, startt.p, nreq.p, mw,
-		                   progressive ? chunk_cnt.p : nullptr, RAW_CNT + nch, opt.ray_cull ? occ_bbox.p : nullptr);  // list lengths + open-ray counts
+		                   sp.progressive ? chunk_cnt.p : nullptr, RAW_CNT + sp.nch, opt.ray_cull ? occ_bbox.p : nullptr);  // list lengths + open-ray counts
 		launch_march_write(s, MAX_RAYS, st.p, ds, rays.p, mw, nreq.p, base.p, numsteps.p, coords.p, nullptr, max_samples, scan,
-		                   progressive && !sorted_rays ? &r0 : nullptr, dbg_lds_fill);
+		                   sp.progressive && !sp.sorted_rays ? &r0 : nullptr, dbg_lds_fill);
 		const RaySort rsort{rs_hist.p, rs_off.p, rs_key.p, rs_perm.p, chunk_cnt.p + RS_N_PERM};
 		const RaySplit split{cutw.p + CW_EST, ccount.p, cutw.p, MAX_RAYS, max_samples};
-		if (sorted_rays)
-			launch_ray_sort(s, MAX_RAYS, numsteps.p, coords.p, ce[0], rsort, chunk_list.p, chunk_cnt.p, scan, scan_tmp_bytes, cut ? &split : nullptr);
+		if (sp.sorted_rays)
+			launch_ray_sort(s, MAX_RAYS, numsteps.p, coords.p, sp.ends[0], rsort, chunk_list.p, chunk_cnt.p, scan, scan_tmp_bytes, sp.cut ? &split : nullptr);
 	}
 
 	LossWork loss_work(const uint32_t* rbase) {
@@ -1835,8 +1783,7 @@ struct NeusTestbed {
 		ek_loss = pin[1] * scale;
 		mask_loss = pin[2] * scale;
 		last_rays_with_samples = sst->rays_ws_global;
-		last_keep_ratio = sst->n_kept ? measured / (float)sst->n_kept : 1.f;  // composited / kept (progressive inference)
-		choose_chunk_ends(sst->compacted_global, sst->rays_ws_global);
+		sched.on_readback(sst->compacted_global, sst->rays_ws_global, sst->n_kept, x.world());
 		ray_loss = sst->rays_ws_global ? pin[0] * (float)(sst->rays_per_batch * x.world()) / (float)sst->rays_ws_global : 0.f;
 		if (!loss_ema_init) { loss_scalar_ema = last_loss; loss_ema_init = true; }
 		else loss_scalar_ema = 0.99f * loss_scalar_ema + 0.01f * last_loss;
@@ -1973,7 +1920,7 @@ int neus_testbed_get_stats(NeusTestbed* tb, NeusTrainStats* o) {
 		o->training_aborted = (tb->aborted || (tb->training_step > 0 && s.zero_records)) ? 1u : 0u;
 		o->pre_samples_total = s.pre_total; o->rays_total = s.rays_total;
 		o->occ_samples_total = tb->occ_samples; o->occ_updates = tb->occ_updates;
-		o->progressive_chunk_end = tb->chunk_ends.empty() ? 0u : tb->chunk_ends[0];
+		o->progressive_chunk_end = tb->sched.ends.empty() ? 0u : tb->sched.ends[0];
 		o->lookahead_steps = tb->la_steps;
 		o->cut_steps = tb->cut_steps;
 		o->march_cut_steps = tb->mcut_steps;
@@ -2240,16 +2187,7 @@ int neus_testbed_get_training_options(NeusTestbed* tb, NeusTrainingOptions* o) {
 }
 int neus_testbed_set_progressive_inference(NeusTestbed* tb, int mode, const uint32_t* chunk_ends, uint32_t n_ends) {
 	return guard([&] {
-		if (mode < 0 || mode > 2) throw std::runtime_error("progressive inference mode must be 0 (off), 1 (auto) or 2 (always)");
-		if (chunk_ends && n_ends) {
-			if (n_ends > 14) throw std::runtime_error("at most 14 chunk ends");
-			for (uint32_t k = 0; k < n_ends; ++k)
-				if (chunk_ends[k] == 0 || (k && chunk_ends[k] <= chunk_ends[k - 1])) throw std::runtime_error("chunk ends must increase from >= 1");
-			tb->chunk_ends.assign(chunk_ends, chunk_ends + n_ends);
-			tb->chunk_ends_cut.clear();
-			tb->chunk_auto = false;
-		}
-		tb->progressive_mode = mode;
+		tb->sched.set(mode, chunk_ends, n_ends);
 	});
 }
 

@@ -93,7 +93,7 @@ def test_bench_step_bitwise_under_lds_garbage_and_concurrency(torch_cuda):
 
 def test_lookahead_sampling_bitwise(torch_cuda):
     """The next step's ray sampling issued beside the current step's backward (the default; NEUS_LOOKAHEAD=0 turns it
-    off, testbed.cpp la_go) gives the step the same samples: from one initialisation, 300 steps in one call (occupancy
+    off, step_plan.h StepPlan::la_go) gives the step the same samples: from one initialisation, 300 steps in one call (occupancy
     updates and loss readbacks, where the lookahead pauses, included) end with bitwise equal parameters, EMA weights,
     occupancy grid and per-ray counts, with and without it."""
     from neus2_amd import pyngp, scenes

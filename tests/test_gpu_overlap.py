@@ -174,7 +174,7 @@ def _same_run(a, b):
 
 
 def test_march_cut_bitwise(torch_cuda):
-    """The march cut (testbed.cpp march_cut_for): a cut step generates and marches only the ray slots below
+    """The march cut (step_plan.h plan_sampling: mcut): a cut step generates and marches only the ray slots below
     the compaction cut's estimate. At the bench's shape, 600 steps in one call with it (the default), without it
     (NEUS_MARCH_CUT=0) and with neither it nor the compaction cut (NEUS_PROG_CUT=0): bitwise the same parameters,
     gradients, EMA weights, occupancy grid and last-step counters; the march was cut on most steps; a failed witness
